@@ -53,6 +53,46 @@ def test_bench_json_line_contract():
     assert c["reference_python"]["value"] == 756.0 and "BASELINE.md" in c["reference_python"]["provenance"]
 
 
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """--dump-outputs: the outputs of the last timed step, identical from run to run with the same
+    arguments, and what the oracle computes from the same seeded batch (10 fixed iterations)."""
+    import numpy as np
+    from helpers import batch_rel_err
+    from ilqr_iterative_tasks_amd import workloads
+    from oracle import oracle as orc
+    dumps = []
+    for name in ("a", "b"):
+        out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "2",
+                              "--no-extra", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / name)],
+                             capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 2
+        info = d["dump_outputs"]
+        assert info["batch"] == 1024 and not info["sampled"] and info["bytes"] <= 64_000_000
+        dumps.append({f.stem: np.load(f) for f in (tmp_path / name).glob("*.npy")})
+    a, b = dumps
+    assert set(a) == set(b) == {"X", "U", "lamb", "cost", "iters", "status", "K_feedback",
+                                "k_feedforward", "cost_it", "best_idx", "best_cost"}
+    for key in a:
+        assert a[key].dtype == np.float64, key
+        np.testing.assert_array_equal(a[key], b[key], err_msg=key)
+    assert a["X"].shape == (1024, 6, 21) and a["U"].shape == (1024, 2, 20)
+    assert (a["iters"] == 10).all()
+    first = int(np.argmin(a["cost_it"]))
+    assert a["best_idx"].tolist() == [first] and a["best_cost"].tolist() == [a["cost_it"][first]]
+    cfg = workloads.config_for("config2")
+    host = workloads.make_batch(cfg, 1024)
+    ref = orc.ilqr_batch(cfg, host["X"], host["U"], host["x_term"], host["lamb"], host["obs"],
+                         max_iter=10, early_exit=False)
+    same = a["lamb"] == ref["lamb"]
+    assert same.mean() > 0.99
+    for key in ("X", "U"):
+        assert batch_rel_err(a[key][same], ref[key][same]) < 1e-8, key
+
+
 CLAIMS = ("large_batch_B65536_f64_frac", "large_batch_B131072_f64_frac", "f32_B65536_frac",
           "quad12_frac", "quad12_Mits", "quad12_f32_frac", "sharded_step_ms", "unsharded_step_ms",
           "sharded_host_enqueue_ms", "sharded_over_unsharded", "sharded_over_unsharded_B131072",
@@ -72,6 +112,8 @@ def test_default_bench_line_carries_the_claim_scalars_at_the_head_of_roofline():
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
+    # the whole line fits a reader that keeps a bounded 16 KiB window of the output
+    assert len(lines[0].encode()) < 15 * 1024, len(lines[0].encode())
     d = json.loads(lines[0])
     r = d["roofline"]
     kept = {}
