@@ -22,8 +22,9 @@ template <class T> hipError_t group_iterate(const i2lqr_config& cfg, const IterA
 // in rounds of kGroup16Batch — wherever whole rounds beat the other forms (above kGroupWsTop).
 constexpr int64_t kGroup16Batch = 4096;
 bool group16_supported(const i2lqr_config& cfg);
+// overlap = false: the one-helper schedule wherever the launcher would pick the overlapped one
 template <class T> hipError_t group16_iterate(const i2lqr_config& cfg, const IterArgs<T>& a,
-                                              hipStream_t stream);
+                                              hipStream_t stream, bool overlap = true);
 
 // Workspace form of the same kernel (records and gains in a caller-provided HBM workspace of
 // group_workspace_bytes() for B problems: 4 KB of LDS per problem, four wavefronts per CU): the

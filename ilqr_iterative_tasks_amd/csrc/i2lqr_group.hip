@@ -58,11 +58,15 @@ hipError_t launch_h(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s
 // Sixteen lanes per problem (one problem per DPP row, four per wavefront): the backward step
 // exchanges nothing through LDS (GroupWorker::backward_row).  One helper wavefront for the record
 // phase (2 x 16 lanes >= the 21 records of a problem: one round) while that leaves every wavefront
-// a SIMD of its own (<= 512 workgroups = 2048 problems).
+// a SIMD of its own (<= 512 workgroups = 2048 problems).  Overlapped schedule (k_group_iterate<..,
+// 3, false, 16>; overlap = false forces the one-helper form): two helpers take all the records
+// while the main wavefront computes the terminal block, and they store the gains at exit — while
+// every workgroup has a CU to itself (<= 256 workgroups = 1024 problems: three SIMDs of four).
 template <class T, class Sys>
-hipError_t launch16(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s) {
+hipError_t launch16(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s, bool overlap) {
   const int64_t cus = device_geometry().cus;
 #ifndef I2LQR_STAMPS
+  if (overlap && (a.B + 3) / 4 <= cus) return launch_h<T, Sys, 3, 16>(cfg, a, s);
   if ((a.B + 3) / 4 <= 2 * cus) return launch_h<T, Sys, 2, 16>(cfg, a, s);
 #endif
   return launch_h<T, Sys, 1, 16>(cfg, a, s);
@@ -219,14 +223,14 @@ bool group16_supported(const i2lqr_config& cfg) {
   return lds <= device_geometry().max_dyn_lds;
 }
 template <> hipError_t group16_iterate<double>(const i2lqr_config& cfg, const IterArgs<double>& a,
-                                               hipStream_t s) {
-  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch16<double, Bicycle4<double>>(cfg, a, s);
-  return launch16<double, Bicycle6<double>>(cfg, a, s);
+                                               hipStream_t s, bool overlap) {
+  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch16<double, Bicycle4<double>>(cfg, a, s, overlap);
+  return launch16<double, Bicycle6<double>>(cfg, a, s, overlap);
 }
 template <> hipError_t group16_iterate<float>(const i2lqr_config& cfg, const IterArgs<float>& a,
-                                              hipStream_t s) {
-  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch16<float, Bicycle4<float>>(cfg, a, s);
-  return launch16<float, Bicycle6<float>>(cfg, a, s);
+                                              hipStream_t s, bool overlap) {
+  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch16<float, Bicycle4<float>>(cfg, a, s, overlap);
+  return launch16<float, Bicycle6<float>>(cfg, a, s, overlap);
 }
 
 bool group_supported(const i2lqr_config& cfg) {

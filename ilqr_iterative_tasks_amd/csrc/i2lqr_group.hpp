@@ -643,26 +643,41 @@ template <class T, class Sys, bool WS = false, int G = kGroup> struct GroupWorke
   //    + 20 16-byte reads; 1293 cycles) with eight lanes per problem.
   template <bool GENERAL>
   __device__ __forceinline__ bool backward_row(int XUo, const T (&xT)[n], T lamb, bool commit) const {
+    T vb[n];
+    terminal_base(XUo, xT, vb);
+    return backward_row_from<GENERAL>(vb, lamb, commit);
+  }
+  // Terminal value function, get_cost_final(): control/ilqr_helper.py:106-150 — the lane's column
+  // of [2 Qt | 2 Qt (x_N - x_T)] before the obstacle terms of record N.  It depends on the nominal's
+  // x_N only, so the overlapped schedule of k_group_iterate computes it while the helpers compute
+  // the records and keeps it over rejected iterations.
+  __device__ __forceinline__ void terminal_base(int XUo, const T (&xT)[n], T (&vb)[n]) const {
+    T dx[n];
+#pragma unroll
+    for (int i = 0; i < n; i++) dx[i] = S[XUo + N * W + i] - xT[i];
+    // column g of 2 Qt by a per-lane LDS address (lanes past the columns read column 0 and drop
+    // it) instead of a chain of selects over the whole matrix; the gradient 2 Qt (x_N - x_T) in
+    // the same operation order as the other kernel families
+    const int gq = g < n ? g : 0;
+#pragma unroll
+    for (int i = 0; i < n; i++) {
+      T vx = T(0);
+#pragma unroll
+      for (int r = 0; r < n; r++) vx += (T(2) * Qt[i * n + r]) * dx[r];
+      const T vxx = T(2) * Qt[i * n + gq];
+      vb[i] = (g == n) ? vx : (g < n ? vxx : T(0));
+    }
+  }
+  // the pass from the terminal block vb (terminal_base() of the nominal the records belong to)
+  template <bool GENERAL>
+  __device__ __forceinline__ bool backward_row_from(const T (&vb)[n], T lamb, bool commit) const {
     static_assert(GL::KW > n + 1, "the padding word of a gain row takes the stores of idle lanes");
     bool bad = false;
     T va[n];
     {
       const T* Rn = rec(N);
-      T dx[n];
 #pragma unroll
-      for (int i = 0; i < n; i++) dx[i] = S[XUo + N * W + i] - xT[i];
-      // column g of 2 Qt by a per-lane LDS address (lanes past the columns read column 0 and drop
-      // it) instead of a chain of selects over the whole matrix; the gradient 2 Qt (x_N - x_T) in
-      // the same operation order as the other kernel families
-      const int gq = g < n ? g : 0;
-#pragma unroll
-      for (int i = 0; i < n; i++) {
-        T vx = T(0);
-#pragma unroll
-        for (int r = 0; r < n; r++) vx += (T(2) * Qt[i * n + r]) * dx[r];
-        const T vxx = T(2) * Qt[i * n + gq];
-        va[i] = (g == n) ? vx : (g < n ? vxx : T(0));
-      }
+      for (int i = 0; i < n; i++) va[i] = vb[i];
       va[0] += Rn[off_l0];
       va[1] += Rn[off_l1];
     }
@@ -1017,7 +1032,7 @@ __device__ __forceinline__ int idx_div(int e, int d, float rcp_d) {
 // horizon — the per-step records (prep): 21 records of eight problems are three rounds for one
 // wavefront and one round for three.  They sleep at a workgroup barrier the rest of the time (a
 // batch of 1024 problems leaves seven of eight SIMDs idle anyway).  Same values whoever computes
-// a record: bit-identical to H = 1.
+// a record: bit-identical to H = 1.  Sixteen lanes with H >= 3: the overlapped schedule (OVL).
 // WS: records and gains in the HBM workspace `ws` (GLayout::ws_words() words per problem, sized for
 // whole wavefronts: ceil(B / 8) * 8 problems), four wavefronts per CU instead of two — the form
 // for more than 4096 problems on the problem-major layout.  Same arithmetic, bit-identical.
@@ -1026,6 +1041,13 @@ __global__ __launch_bounds__(64 * H) void k_group_iterate(const DevCfg<T, Sys::n
                                                           const IterArgs<T> a, T* ws = nullptr) {
   static_assert(!(WS && H > 1), "the workspace form runs without helper wavefronts");
   constexpr int n = Sys::n, m = Sys::m, W = n + m;
+  // overlapped schedule (sixteen lanes, H >= 3): the helpers compute all the records while the
+  // main wavefront computes the terminal block, and they store the gains at exit
+#ifdef I2LQR_STAMPS
+  constexpr bool OVL = false;  // (the stamped build times the lone wavefront)
+#else
+  constexpr bool OVL = G == 16 && H >= 3;
+#endif
   using GL = GLayout<Sys, G>;
   extern __shared__ __align__(16) unsigned char gsmem_raw[];
   T* smem = reinterpret_cast<T*>(gsmem_raw);
@@ -1073,20 +1095,50 @@ __global__ __launch_bounds__(64 * H) void k_group_iterate(const DevCfg<T, Sys::n
   int* const ctl = reinterpret_cast<int*>(smem + L.ctl_base());
   if constexpr (H > 1) {
     if (hv > 0) {  // helper: its share of the records whenever the main wavefront asks for them
+      // (OVL: the helpers take all of them, the main wavefront none)
+      const int h0 = OVL ? hv - 1 : hv, hs = OVL ? H - 1 : H;
       for (;;) {
         __syncthreads();  // B1: the control words of this iteration are written
         const int flags = ctl[8];
         if (!(flags & 1)) break;
         if (flags & 2) {
           const int pc = ctl[lane / G];
-          w.prep(pc ? L.XU1 : L.XU0, pc ? L.TR1 : L.TR0, ob, ob_pa, ob_pb, hv * G + g,
-                 H * G);
+          w.prep(pc ? L.XU1 : L.XU0, pc ? L.TR1 : L.TR0, ob, ob_pa, ob_pb, h0 * G + g, hs * G);
         }
         __syncthreads();  // B2: the records are complete
+      }
+      // OVL exit: the gains of the problem's last executed iteration (complete in LDS since the
+      // barrier above) -> K[a][j][t], k[a][t]; lane g of helper h takes the steps t = (h - 1) G + g,
+      // t + (H - 1) G, ...: per step every word is a compile-time offset, and the sixteen lanes of a
+      // problem store sixteen consecutive t of each row
+      if constexpr (OVL) {
+        if (real && a.K) {
+          T* const gK = a.K + prob * (int64_t)(m * n * N);
+          T* const gk = a.k + prob * (int64_t)(m * N);
+          for (int t = h0 * G + g; t < N; t += hs * G) {
+            const T* Kt = w.gain(t);
+            T kv[m][n + 1];
+#pragma unroll
+            for (int aa = 0; aa < m; aa++)
+#pragma unroll
+              for (int j = 0; j <= n; j++) kv[aa][j] = Kt[aa * GL::KW + j];
+#pragma unroll
+            for (int aa = 0; aa < m; aa++) {
+#pragma unroll
+              for (int j = 0; j < n; j++) gK[(aa * n + j) * N + t] = kv[aa][j];
+              gk[aa * N + t] = kv[aa][n];
+            }
+          }
+        }
       }
       return;
     }
   }
+  // OVL: the terminal block of the nominal (GroupWorker::terminal_base), computed by the main
+  // wavefront while the helpers compute the records, kept over rejected iterations
+  T vb[n];
+#pragma unroll
+  for (int i = 0; i < n; i++) vb[i] = T(0);
   T cost = w.rollout(L.XU0, L.TR0, xT);
   int it = 0, status = a.early_exit ? 2 /*MAX_ITER*/ : 0 /*RUNNING*/;
   T cost_ret = cost;
@@ -1113,15 +1165,24 @@ __global__ __launch_bounds__(64 * H) void k_group_iterate(const DevCfg<T, Sys::n
       if (g == 0) ctl[lane / G] = cur;
       if (lane == 0) ctl[8] = 1 | (do_prep ? 2 : 0);
       __syncthreads();  // B1
-      if (do_prep) w.prep(XUo, TRo, ob, ob_pa, ob_pb, g, H * G);
+      if constexpr (OVL) {
+        if (do_prep) w.terminal_base(XUo, xT, vb);
+      } else {
+        if (do_prep) w.prep(XUo, TRo, ob, ob_pa, ob_pb, g, H * G);
+      }
       __syncthreads();  // B2
     } else {
       if (__any(fresh)) w.prep(XUo, TRo, ob, ob_pa, ob_pb, g, G);
     }
 #endif
     // optimistic, branch-free passes first; the general forms only if a lane asked for them
-    if (__builtin_expect(__any(w.template backward<false>(XUo, xT, lamb, active)), 0))
-      w.template backward<true>(XUo, xT, lamb, active);
+    if constexpr (OVL) {
+      if (__builtin_expect(__any(w.template backward_row_from<false>(vb, lamb, active)), 0))
+        w.template backward_row_from<true>(vb, lamb, active);
+    } else {
+      if (__builtin_expect(__any(w.template backward<false>(XUo, xT, lamb, active)), 0))
+        w.template backward<true>(XUo, xT, lamb, active);
+    }
     T cost_new;
     {
 #ifdef I2LQR_STAMPS
@@ -1170,7 +1231,31 @@ __global__ __launch_bounds__(64 * H) void k_group_iterate(const DevCfg<T, Sys::n
   if (!t_isfinite(cost_ret)) status = 4;
 
   // exit: X, U, gains, scalars (LDS -> HBM, problem-major records with time contiguous)
-  if (real) {
+  if (OVL && real) {
+    // X[i][t], U[a][t] from record t of the nominal: lane g takes t = g, g + G, ... (compile-time
+    // offsets, consecutive t on consecutive lanes); the gains are the helpers' (above)
+    const int XUo = cur ? L.XU1 : L.XU0;
+    T* const gX = a.X + prob * (int64_t)(n * (N + 1));
+    T* const gU = a.U + prob * (int64_t)(m * N);
+    for (int t = g; t <= N; t += G) {
+      T xu[W];
+#pragma unroll
+      for (int i = 0; i < W; i++) xu[i] = S[XUo + t * W + i];  // (u of t = N: unused input slot)
+#pragma unroll
+      for (int i = 0; i < n; i++) gX[i * (N + 1) + t] = xu[i];
+      if (t < N) {
+#pragma unroll
+        for (int aa = 0; aa < m; aa++) gU[aa * N + t] = xu[n + aa];
+      }
+    }
+    if (g == 0) {
+      a.lamb[prob] = lamb;
+      a.cost[prob] = cost_ret;
+      if (a.iters) a.iters[prob] = it;
+      if (a.status) a.status[prob] = status;
+    }
+  }
+  if (!OVL && real) {
     const int XUo = cur ? L.XU1 : L.XU0;
     T* gX = a.X + prob * (int64_t)(n * (N + 1));
     for (int e = g; e < n * (N + 1); e += G) {

@@ -301,6 +301,11 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     step (records) / two steps (gains) ahead.  Same arithmetic, bit-identical.
  *                     Automatic: above 4096 problems whenever the workspace is registered (below,
  *                     every wavefront has its CU's LDS to itself either way).
+ *   "group_overlap"   sixteen-lane kernel, up to one workgroup of four problems per CU: 0 forces
+ *                     the one-helper schedule; 1 / automatic: two helper wavefronts compute the
+ *                     per-step records while the main wavefront computes the terminal value block
+ *                     (kept over rejected iterations), and the helpers store the gains at exit.
+ *                     Same arithmetic, bit-identical.
  *   "speculate"       ("group_lanes" 8 / automatic) 1: the speculative form of the eight-lane
  *                     kernel — V wavefronts per eight problems (three up to 512 problems, two
  *                     above and in the tail of the chunked solves), wavefront v runs the iteration
