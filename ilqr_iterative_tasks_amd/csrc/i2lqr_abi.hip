@@ -52,6 +52,8 @@ int fail(int code, const char* fmt, ...) {
 }  // namespace
 
 #ifdef I2LQR_DRY_RUN
+#include <cxxabi.h>
+
 #include <string>
 #include <vector>
 namespace i2lqr {
@@ -85,30 +87,58 @@ void reset() {
   st().text.clear();
   st().launches = st().violations = 0;
 }
-void record(const char* kernel, dim3 grid, dim3 block, size_t lds) {
+// the record being built by this thread (launch(): record, the arguments, end)
+thread_local std::string t_line, t_kernel;
+void record(const char* expr, const void* kernel, dim3 grid, dim3 block, size_t lds) {
+  t_kernel = expr;
+  Dl_info info;
+  if (dladdr(kernel, &info) && info.dli_sname && info.dli_saddr == kernel) {
+    int status = 0;
+    char* name = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &status);
+    t_kernel = status == 0 && name ? name : info.dli_sname;
+    free(name);
+  }
+  char line[96];
+  snprintf(line, sizeof(line), " grid %u block %u lds %zu", grid.x, block.x, lds);
+  t_line = "launch " + t_kernel + line;
   std::lock_guard<std::mutex> lock(st().mu);
-  char line[384];
-  snprintf(line, sizeof(line), "launch %.200s grid %u block %u lds %zu\n", kernel, grid.x, block.x, lds);
-  if (st().text.size() < (1u << 15)) st().text += line;
   st().launches++;
   const DeviceGeometry& g = device_geometry();
   if (grid.x == 0 || block.x == 0 || block.x > 1024 || lds > g.max_dyn_lds) {
     st().violations++;
-    snprintf(line, sizeof(line), "VIOLATION %.200s: launch shape grid %u block %u lds %zu\n", kernel,
-             grid.x, block.x, lds);
-    st().text += line;
+    st().text += "VIOLATION " + t_kernel + ": launch shape" + line + "\n";
   }
 }
-void ptr(const char* kernel, const char* field, const void* p) {
-  if (!p) return;
+void ptr(const char* field, const void* p) {
+  char buf[96];
+  if (!p) {
+    snprintf(buf, sizeof(buf), " %s=0", field);
+    t_line += buf;
+    return;
+  }
   std::lock_guard<std::mutex> lock(st().mu);
   const uintptr_t a = (uintptr_t)p;
-  for (const auto& r : st().ranges)
-    if (a >= r.first && a < r.second) return;
+  for (size_t r = 0; r < st().ranges.size(); r++)
+    if (a >= st().ranges[r].first && a < st().ranges[r].second) {
+      snprintf(buf, sizeof(buf), " %s=r%zu+%zu", field, r, (size_t)(a - st().ranges[r].first));
+      t_line += buf;
+      return;
+    }
+  snprintf(buf, sizeof(buf), " %s=?", field);
+  t_line += buf;
   st().violations++;
-  char line[384];
-  snprintf(line, sizeof(line), "VIOLATION %.200s: %s = %p lies in no declared range\n", kernel, field, p);
-  st().text += line;
+  char line[160];
+  snprintf(line, sizeof(line), ": %s = %p lies in no declared range\n", field, p);
+  st().text += "VIOLATION " + t_kernel + line;
+}
+void val(const char* field, int64_t v) {
+  char buf[96];
+  snprintf(buf, sizeof(buf), " %s=%lld", field, (long long)v);
+  t_line += buf;
+}
+void end() {
+  std::lock_guard<std::mutex> lock(st().mu);
+  if (st().text.size() < (1u << 21)) st().text += t_line + "\n";
 }
 int64_t report(char* buf, int64_t n) {
   std::lock_guard<std::mutex> lock(st().mu);
@@ -396,6 +426,33 @@ FusedKernel select_fused(const i2lqr_handle* h, int64_t B, bool early_exit, cons
   return K_WAVE;
 }
 
+// f(std::true_type()) for a device config with stage weights (DevCfg::flags), f(std::false_type())
+// otherwise: the HASQR parameter of the kernel f launches.  BUILT = false where the stage-weight
+// instantiations do not exist (the caller has refused such a configuration): the false one always.
+template <bool BUILT = true, class F> void with_weights(int flags, F&& f) {
+  if constexpr (BUILT) {
+    if (flags) {
+      f(std::true_type());
+      return;
+    }
+  }
+  f(std::false_type());
+}
+
+// IterArgs of a launch on the caller's arrays, every optional field at its neutral value
+template <class T>
+IterArgs<T> iter_args(int64_t B, int n_iters, int early_exit, void* X, void* U, const void* x_term,
+                      void* lamb, const void* obs, void* cost, void* K, void* k, int32_t* iters,
+                      int32_t* status) {
+  IterArgs<T> a;
+  a.B = B; a.n_iters = n_iters; a.early_exit = early_exit;
+  a.X = (T*)X; a.U = (T*)U; a.x_term = (const T*)x_term; a.lamb = (T*)lamb; a.obs = (const T*)obs;
+  a.cost = (T*)cost; a.K = (T*)K; a.k = (T*)k; a.iters = iters; a.status = status;
+  a.dbg = nullptr;
+  a.count = nullptr; a.count_max = 0; a.max_total = 0; a.set_stride = 0;
+  return a;
+}
+
 // One launcher per (dtype, system); LANES fixed at 64 = one problem per wavefront.
 template <class T, class Sys> struct Launch {
   static constexpr int n = Sys::n, m = Sys::m, LANES = 64;
@@ -414,25 +471,14 @@ template <class T, class Sys> struct Launch {
     if (h->lds_bytes > h->geo.max_dyn_lds)
       return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d needs %zu B of LDS per wavefront (> %zu KiB)",
                   h->cfg.N, h->lds_bytes, h->geo.max_dyn_lds / 1024);
-    if (h->lds_bytes > h->geo.default_dyn_lds) {
-      const int bytes = (int)h->lds_bytes;
-      HIP_TRY(hipFuncSetAttribute((const void*)k_iterate<T, Sys, LANES, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_iterate<T, Sys, LANES, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_backward<T, Sys, LANES, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_backward<T, Sys, LANES, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_forward<T, Sys, LANES, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_forward<T, Sys, LANES, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_rollout<T, Sys, LANES, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-      HIP_TRY(hipFuncSetAttribute((const void*)k_rollout<T, Sys, LANES, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    }
+    if (h->lds_bytes > h->geo.default_dyn_lds)
+      for (const void* kernel :
+           {(const void*)k_iterate<T, Sys, LANES, false>, (const void*)k_iterate<T, Sys, LANES, true>,
+            (const void*)k_backward<T, Sys, LANES, false>, (const void*)k_backward<T, Sys, LANES, true>,
+            (const void*)k_forward<T, Sys, LANES, false>, (const void*)k_forward<T, Sys, LANES, true>,
+            (const void*)k_rollout<T, Sys, LANES, false>, (const void*)k_rollout<T, Sys, LANES, true>})
+        HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)h->lds_bytes));
     return I2LQR_OK;
   }
 
@@ -440,22 +486,8 @@ template <class T, class Sys> struct Launch {
                      const void* x_term, void* lamb, const void* obs, void* cost, void* K, void* k,
                      int32_t* iters, int32_t* status, hipStream_t s) {
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    IterArgs<T> a;
-    a.B = B;
-    a.n_iters = n_iters;
-    a.early_exit = early_exit;
-    a.X = (T*)X;
-    a.U = (T*)U;
-    a.x_term = (const T*)x_term;
-    a.lamb = (T*)lamb;
-    a.obs = (const T*)obs;
-    a.cost = (T*)cost;
-    a.K = (T*)K;
-    a.k = (T*)k;
-    a.iters = iters;
-    a.status = status;
-    a.dbg = nullptr;
-    a.count = nullptr; a.count_max = 0; a.max_total = 0; a.set_stride = 0;
+    IterArgs<T> a = iter_args<T>(B, n_iters, early_exit, X, U, x_term, lamb, obs, cost, K, k, iters,
+                                 status);
 #ifdef I2LQR_STAMPS
     a.dbg = (unsigned long long*)h->ws;  // diagnostic build: caller registers [B][8] u64 here
 #endif
@@ -522,22 +554,16 @@ template <class T, class Sys> struct Launch {
                                           : waves_per_cu * lds_f <= h->geo.lds_per_cu - 10 * 1024);
     if constexpr (kHasFstep) {
       if (fstep) {
-        if (c.flags)
-          hipLaunchKernelGGL((k_iterate<T, Sys, LANES, true, true>), dim3(grid(B)), dim3(64), lds_f,
-                             s, c, a);
-        else
-          hipLaunchKernelGGL((k_iterate<T, Sys, LANES, false, true>), dim3(grid(B)), dim3(64), lds_f,
-                             s, c, a);
+        with_weights(c.flags, [&](auto W) {
+          hipLaunchKernelGGL((k_iterate<T, Sys, LANES, W, true>), dim3(grid(B)), dim3(64), lds_f, s, c, a);
+        });
         HIP_TRY(hipGetLastError());
         return I2LQR_OK;
       }
     }
-    if (c.flags)
-      hipLaunchKernelGGL((k_iterate<T, Sys, LANES, true>), dim3(grid(B)), dim3(64), h->lds_bytes, s,
-                         c, a);
-    else
-      hipLaunchKernelGGL((k_iterate<T, Sys, LANES, false>), dim3(grid(B)), dim3(64), h->lds_bytes,
-                         s, c, a);
+    with_weights(c.flags, [&](auto W) {
+      hipLaunchKernelGGL((k_iterate<T, Sys, LANES, W>), dim3(grid(B)), dim3(64), h->lds_bytes, s, c, a);
+    });
     HIP_TRY(hipGetLastError());
     return I2LQR_OK;
   }
@@ -553,12 +579,8 @@ template <class T, class Sys> struct Launch {
                     "bicycle plant with Q = R = 0, at most %lld chains, a horizon whose three-wavefront "
                     "buffers fit a CU's LDS (solve the chain steps one after the other instead)",
                     (long long)h->geo.scaled(512));
-      IterArgs<T> a;
-      a.B = L; a.n_iters = h->cfg.max_iter; a.early_exit = 1;
-      a.X = (T*)X; a.U = (T*)U; a.x_term = (const T*)x_term; a.lamb = (T*)lamb;
-      a.obs = (const T*)obs; a.cost = (T*)cost; a.K = (T*)K; a.k = (T*)kk;
-      a.iters = iters; a.status = status; a.dbg = nullptr;
-      a.count = nullptr; a.count_max = 0; a.max_total = 0; a.set_stride = 0;
+      IterArgs<T> a = iter_args<T>(L, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, kk, iters,
+                                   status);
       a.chain_len = k;
       HIP_TRY(group_spec_chain<T>(h->cfg, a, s));
       return I2LQR_OK;
@@ -568,26 +590,21 @@ template <class T, class Sys> struct Launch {
   static int rollout(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term, void* cost,
                      hipStream_t s) {
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    if (c.flags)
-      hipLaunchKernelGGL((k_rollout<T, Sys, LANES, true>), dim3(grid(B)), dim3(64), h->lds_bytes, s,
-                         c, B, (T*)X, (T*)U, (const T*)x_term, (T*)cost);
-    else
-      hipLaunchKernelGGL((k_rollout<T, Sys, LANES, false>), dim3(grid(B)), dim3(64), h->lds_bytes,
-                         s, c, B, (T*)X, (T*)U, (const T*)x_term, (T*)cost);
+    with_weights(c.flags, [&](auto W) {
+      hipLaunchKernelGGL((k_rollout<T, Sys, LANES, W>), dim3(grid(B)), dim3(64), h->lds_bytes, s, c,
+                         B, (T*)X, (T*)U, (const T*)x_term, (T*)cost);
+    });
     HIP_TRY(hipGetLastError());
     return I2LQR_OK;
   }
   static int backward(i2lqr_handle* h, int64_t B, const void* X, const void* U, const void* x_term,
                       const void* lamb, const void* obs, void* K, void* k, hipStream_t s) {
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    if (c.flags)
-      hipLaunchKernelGGL((k_backward<T, Sys, LANES, true>), dim3(grid(B)), dim3(64), h->lds_bytes,
-                         s, c, B, (const T*)X, (const T*)U, (const T*)x_term, (const T*)lamb,
+    with_weights(c.flags, [&](auto W) {
+      hipLaunchKernelGGL((k_backward<T, Sys, LANES, W>), dim3(grid(B)), dim3(64), h->lds_bytes, s, c,
+                         B, (const T*)X, (const T*)U, (const T*)x_term, (const T*)lamb,
                          (const T*)obs, (T*)K, (T*)k);
-    else
-      hipLaunchKernelGGL((k_backward<T, Sys, LANES, false>), dim3(grid(B)), dim3(64), h->lds_bytes,
-                         s, c, B, (const T*)X, (const T*)U, (const T*)x_term, (const T*)lamb,
-                         (const T*)obs, (T*)K, (T*)k);
+    });
     HIP_TRY(hipGetLastError());
     return I2LQR_OK;
   }
@@ -595,14 +612,11 @@ template <class T, class Sys> struct Launch {
                      const void* K, const void* k, void* Xn, void* Un, void* cost_new,
                      hipStream_t s) {
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    if (c.flags)
-      hipLaunchKernelGGL((k_forward<T, Sys, LANES, true>), dim3(grid(B)), dim3(64), h->lds_bytes, s,
-                         c, B, (const T*)X, (const T*)U, (const T*)x_term, (const T*)K,
-                         (const T*)k, (T*)Xn, (T*)Un, (T*)cost_new);
-    else
-      hipLaunchKernelGGL((k_forward<T, Sys, LANES, false>), dim3(grid(B)), dim3(64), h->lds_bytes,
-                         s, c, B, (const T*)X, (const T*)U, (const T*)x_term, (const T*)K,
-                         (const T*)k, (T*)Xn, (T*)Un, (T*)cost_new);
+    with_weights(c.flags, [&](auto W) {
+      hipLaunchKernelGGL((k_forward<T, Sys, LANES, W>), dim3(grid(B)), dim3(64), h->lds_bytes, s, c,
+                         B, (const T*)X, (const T*)U, (const T*)x_term, (const T*)K, (const T*)k,
+                         (T*)Xn, (T*)Un, (T*)cost_new);
+    });
     HIP_TRY(hipGetLastError());
     return I2LQR_OK;
   }
@@ -617,6 +631,27 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
   static constexpr int n = Sys::n, m = Sys::m, NT = Sys::NTRIG;
   using Cfg = DevCfg<T, n, m>;
   static unsigned grid(int64_t B) { return (unsigned)((B + 63) / 64); }
+  // the caller's arrays as a set (K, k, iters, status may be null)
+  static LaneSet<T> user_set(int64_t B, void* X, void* U, const void* x_term, void* lamb,
+                             const void* obs, void* cost, void* K, void* k, int32_t* iters,
+                             int32_t* status) {
+    return LaneSet<T>{(T*)X, (T*)U, (T*)x_term, (T*)obs, (T*)lamb, (T*)cost, (T*)K, (T*)k,
+                      iters, status, nullptr, B};
+  }
+  // the entry fields of a launch on the arrays of `w` (the caller's or a work set)
+  static void set_io(LaneArgs<T>& a, int n_iters, int early_exit, const LaneSet<T>& w) {
+    a.B = w.B; a.n_iters = n_iters; a.early_exit = early_exit;
+    a.X = w.X; a.U = w.U; a.x_term = w.x_term; a.lamb = w.lamb; a.obs = w.obs; a.cost = w.cost;
+    a.K = w.K; a.k = w.k; a.iters = w.iters; a.status = w.status;
+  }
+  // i2lqr_solve of B problems runs as the chunked solve (solve_compacting).  Automatic: from 4096
+  // problems with more than 16 iterations allowed (measured 1.2-1.9x on the bench workload from
+  // 4096 to 262144 problems; the chunks alone cost ~9 % when nothing terminates early).
+  static bool chunked(const i2lqr_handle* h, int64_t B) {
+    const int64_t cmin = h->compact_min_batch < 0
+        ? (h->cfg.max_iter > 16 ? h->geo.scaled(kAutoCompactBatch) : 0) : h->compact_min_batch;
+    return cmin > 0 && B >= cmin && h->cfg.max_iter > 4;
+  }
   // Workspace (bytes) for B problems: candidate trajectory + gains scratch (every call), and for
   // the chunked solve two compacted work sets, scratch iters/status and one counter per round.
   static constexpr int kMaxRounds = 24;  // compaction rounds of the chunked solve (one counter each)
@@ -641,14 +676,9 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
   // (round 5: instantiations of their own, i2lqr_lane12qr.hip)
   static constexpr bool kStageWeights = Sys::NBLK == 0 || sizeof(T) == 8;
   static int need_ws(i2lqr_handle* h, int64_t B) {
-    if constexpr (!kStageWeights) {
-      bool hasqr = false;
-      for (int i = 0; i < I2LQR_MAX_N * I2LQR_MAX_N && !hasqr; i++) hasqr = h->cfg.Q[i] != 0.0;
-      for (int i = 0; i < I2LQR_MAX_M * I2LQR_MAX_M && !hasqr; i++) hasqr = h->cfg.R[i] != 0.0;
-      if (hasqr)
-        return fail(I2LQR_ERR_UNSUPPORTED, "the one-problem-per-lane kernels of this plant are built "
-                    "for Q = R = 0 (use the problem-major layout for stage weights)");
-    }
+    if (!kStageWeights && has_stage_weights(h->cfg))
+      return fail(I2LQR_ERR_UNSUPPORTED, "the one-problem-per-lane kernels of this plant are built "
+                  "for Q = R = 0 (use the problem-major layout for stage weights)");
     if (TILED && (B & 63))
       return fail(I2LQR_ERR_INVALID, "the batch-tiled layout needs a batch that is a multiple of "
                   "64 (got %lld)", (long long)B);
@@ -756,10 +786,8 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
   // roof).  Its segment buffer takes the place of LDS-resident gain steps.  Must be called again
   // after any later change of defer / reroll / merge (the early-exit path does).
   static void finish_options(const i2lqr_handle* h, int64_t B, LaneArgs<T>& a) {
-    bool hasqr = false;
-    for (int i = 0; i < I2LQR_MAX_N * I2LQR_MAX_N && !hasqr; i++) hasqr = h->cfg.Q[i] != 0.0;
-    for (int i = 0; i < I2LQR_MAX_M * I2LQR_MAX_M && !hasqr; i++) hasqr = h->cfg.R[i] != 0.0;
-    const bool can = sizeof(T) == 8 && !hasqr && a.defer && a.merge && a.reroll && h->cfg.N >= 2;
+    const bool can = sizeof(T) == 8 && !has_stage_weights(h->cfg) && a.defer && a.merge && a.reroll &&
+                     h->cfg.N >= 2;
     // (tools/ab_bench.py --cold, round 3: -2 % at 65536 problems, +-0 at 131072, +5 % at 262144,
     // +4-6 % at 2^20; HBM bytes per problem-iteration 6993 -> 6243 (1.41 -> 1.26 x algorithmic):
     // on from 65536 problems, BASELINE's roofline batch and half a per-GPU shard of configs[3] —
@@ -828,19 +856,14 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
                           unsigned workgroups, hipStream_t s) {
     if constexpr (Sys::NBLK == 0) {
       LaneArgs<T> ap = a;
-      if (c.flags) {  // stage weights: the record carries 2 Q (x_t - xtarget) as well
-        using LW = LaneWorker<T, Sys, true, TL>;
+      // stage weights: the record carries 2 Q (x_t - xtarget) as well
+      with_weights(c.flags, [&](auto W) {
+        using LW = LaneWorker<T, Sys, W, TL>;
         const size_t fixed = 2 * LW::kRec * 64 * sizeof(T) + 65 * sizeof(int) + 12;
-        grow_lds(g, &k_lane_iterate_pair<T, Sys, true, TL>, c, ap, workgroups, fixed);
-        hipLaunchKernelGGL((k_lane_iterate_pair<T, Sys, true, TL>), dim3(workgroups), dim3(128),
+        grow_lds(g, &k_lane_iterate_pair<T, Sys, W, TL>, c, ap, workgroups, fixed);
+        hipLaunchKernelGGL((k_lane_iterate_pair<T, Sys, W, TL>), dim3(workgroups), dim3(128),
                            lane_lds(ap) + fixed, s, c, ap);
-      } else {
-        using LW = LaneWorker<T, Sys, false, TL>;
-        const size_t fixed = 2 * LW::kRec * 64 * sizeof(T) + 65 * sizeof(int) + 12;
-        grow_lds(g, &k_lane_iterate_pair<T, Sys, false, TL>, c, ap, workgroups, fixed);
-        hipLaunchKernelGGL((k_lane_iterate_pair<T, Sys, false, TL>), dim3(workgroups), dim3(128),
-                           lane_lds(ap) + fixed, s, c, ap);
-      }
+      });
     }
   }
   template <bool TL>
@@ -851,26 +874,16 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
       return;
     }
     if constexpr (Sys::NBLK > 0) {  // row-block plants: their own fused kernel, no LDS
-      bool launched = false;
-      if constexpr (kStageWeights) {  // (need_ws() has refused stage weights where they are not built)
-        if (c.flags) {
-          hipLaunchKernelGGL((k_lane_iterate_rows<T, Sys, true, TL>), dim3(grid(B)), dim3(64), 0, s, c, a);
-          launched = true;
-        }
-      }
-      if (!launched)
-        hipLaunchKernelGGL((k_lane_iterate_rows<T, Sys, false, TL>), dim3(grid(B)), dim3(64), 0, s, c, a);
+      with_weights<kStageWeights>(c.flags, [&](auto W) {
+        hipLaunchKernelGGL((k_lane_iterate_rows<T, Sys, W, TL>), dim3(grid(B)), dim3(64), 0, s, c, a);
+      });
     } else {
       LaneArgs<T> ag = a;
-      if (c.flags) {
-        grow_lds(g, &k_lane_iterate<T, Sys, true, TL>, c, ag, grid(B), 0);
-        hipLaunchKernelGGL((k_lane_iterate<T, Sys, true, TL>), dim3(grid(B)), dim3(64),
-                           lane_lds(ag), s, c, ag);
-      } else {
-        grow_lds(g, &k_lane_iterate<T, Sys, false, TL>, c, ag, grid(B), 0);
-        hipLaunchKernelGGL((k_lane_iterate<T, Sys, false, TL>), dim3(grid(B)), dim3(64),
-                           lane_lds(ag), s, c, ag);
-      }
+      with_weights(c.flags, [&](auto W) {
+        grow_lds(g, &k_lane_iterate<T, Sys, W, TL>, c, ag, grid(B), 0);
+        hipLaunchKernelGGL((k_lane_iterate<T, Sys, W, TL>), dim3(grid(B)), dim3(64), lane_lds(ag), s,
+                           c, ag);
+      });
     }
   }
 
@@ -907,13 +920,9 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     LaneArgs<T> a0;
     Carved cv;
     carve(h, B, a0, &cv);
-    LaneSet<T> usr;
-    usr.B = B;
-    usr.X = (T*)X; usr.U = (T*)U; usr.x_term = (T*)x_term; usr.obs = (T*)obs;
-    usr.lamb = (T*)lamb; usr.cost = (T*)cost; usr.K = (T*)K; usr.k = (T*)k;
-    usr.iters = iters ? iters : cv.uiters;
-    usr.status = status ? status : cv.ustatus;
-    usr.orig = nullptr;
+    LaneSet<T> usr = user_set(B, X, U, x_term, lamb, obs, cost, K, k, iters, status);
+    if (!iters) usr.iters = cv.uiters;
+    if (!status) usr.status = cv.ustatus;
     if (!obs) { cv.set[0].obs = nullptr; cv.set[1].obs = nullptr; }
     // Latency tail: once few problems survive, the rest of the solve is bound by the slowest
     // problem's iteration latency, which is ~2.8x lower with one problem per WAVEFRONT.  If the
@@ -935,9 +944,7 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     const int first = h->opt_first_chunk > 0 ? h->opt_first_chunk : kFirstChunk;
     int done = 0, len = max_iter < first ? max_iter : first;
     const int step = h->opt_chunk_step > 0 ? h->opt_chunk_step : 4;
-    a0.B = B; a0.n_iters = len; a0.early_exit = 1;
-    a0.X = usr.X; a0.U = usr.U; a0.x_term = usr.x_term; a0.lamb = usr.lamb; a0.obs = usr.obs;
-    a0.cost = usr.cost; a0.K = usr.K; a0.k = usr.k; a0.iters = usr.iters; a0.status = usr.status;
+    set_io(a0, len, 1, usr);
     a0.max_total = max_iter;
     // one live counter per compaction round, all cleared by ONE fill in front of the first chunk (a
     // fill per round was a 5 us launch of its own in each of the rounds that follow the tail)
@@ -989,11 +996,8 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
       if (wave_tail > 0 && done >= 4) {
         using WL = Launch<T, Sys>;
         const size_t lds_f = WL::fstep_lds_bytes(N);
-        IterArgs<T> t;
-        t.B = B; t.n_iters = max_iter; t.early_exit = 1;
-        t.X = w.X; t.U = w.U; t.x_term = w.x_term; t.lamb = w.lamb; t.obs = w.obs;
-        t.cost = w.cost; t.K = w.K; t.k = w.k; t.iters = w.iters; t.status = w.status;
-        t.dbg = nullptr;
+        IterArgs<T> t = iter_args<T>(B, max_iter, 1, w.X, w.U, w.x_term, w.lamb, w.obs, w.cost, w.K,
+                                     w.k, w.iters, w.status);
         t.count = count; t.count_max = last_round ? (int)B : wave_tail; t.max_total = max_iter;
         t.set_stride = B;
         if (spec_tail) {
@@ -1007,12 +1011,10 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
           if constexpr (m == 2 && n + m <= 8) HIP_TRY(group_spec_tail<T>(h->cfg, t, s));
         } else if (WL::kHasFstep && lds_f <= h->geo.default_dyn_lds) {
           if constexpr (WL::kHasFstep) {
-            if (c.flags)
-              hipLaunchKernelGGL((k_iterate<T, Sys, 64, true, true, true>), dim3(wave_tail),
-                                 dim3(64), lds_f, s, c, t);
-            else
-              hipLaunchKernelGGL((k_iterate<T, Sys, 64, false, true, true>), dim3(wave_tail),
-                                 dim3(64), lds_f, s, c, t);
+            with_weights(c.flags, [&](auto W) {
+              hipLaunchKernelGGL((k_iterate<T, Sys, 64, W, true, true>), dim3(wave_tail), dim3(64),
+                                 lds_f, s, c, t);
+            });
           }
         }
       }
@@ -1029,10 +1031,9 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
       len = done < 12 ? step : done;
       if (done + len > max_iter || round + 2 >= kMaxRounds) len = max_iter - done;
       LaneArgs<T> a = a0;
-      a.X = w.X; a.U = w.U; a.x_term = w.x_term; a.lamb = w.lamb; a.obs = w.obs; a.cost = w.cost;
+      set_io(a, len, 1, w);
       a.K = nullptr; a.k = nullptr;  // gains of work sets go to the scratch buffer (w.K == wsK)
-      a.iters = w.iters; a.status = w.status;
-      a.count = count; a.resume = 1; a.n_iters = len;
+      a.count = count; a.resume = 1;
       // the chunk's exit packs its survivors into the OTHER work set (none behind the last chunk)
       plan_exit(a, false, w.orig, done + len >= max_iter ? nullptr : &cv.set[cur ^ 1],
                 cv.count + round + 1);
@@ -1075,21 +1076,13 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
   static int iterate(i2lqr_handle* h, int64_t B, int n_iters, int early_exit, void* X, void* U,
                      const void* x_term, void* lamb, const void* obs, void* cost, void* K, void* k,
                      int32_t* iters, int32_t* status, hipStream_t s) {
-    // automatic: chunked solve with the speculative tail from 4096 problems and more than 16
-    // iterations allowed (measured 1.2-1.9x on the bench workload from 4096 to 262144 problems;
-    // the chunks alone cost ~9 % when nothing terminates early)
-    const int64_t cmin = h->compact_min_batch < 0
-        ? (h->cfg.max_iter > 16 ? h->geo.scaled(kAutoCompactBatch) : 0) : h->compact_min_batch;
-    if (early_exit && cmin > 0 && B >= cmin && n_iters > 4 && n_iters == h->cfg.max_iter)
+    if (early_exit && n_iters == h->cfg.max_iter && chunked(h, B))
       return solve_compacting(h, B, X, U, x_term, lamb, obs, cost, K, k, iters, status, s);
     if (int rc = need_ws(h, B)) return rc;
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
     LaneArgs<T> a;
     carve(h, B, a);
-    a.B = B; a.n_iters = n_iters; a.early_exit = early_exit;
-    a.X = (T*)X; a.U = (T*)U; a.x_term = (const T*)x_term; a.lamb = (T*)lamb;
-    a.obs = (const T*)obs; a.cost = (T*)cost; a.K = (T*)K; a.k = (T*)k;
-    a.iters = iters; a.status = status;
+    set_io(a, n_iters, early_exit, user_set(B, X, U, x_term, lamb, obs, cost, K, k, iters, status));
     a.max_total = n_iters;
     if (early_exit) {  // solve() is bound by its slowest problem's latency, not by HBM traffic
       if (h->opt_reroll < 0) a.reroll = 0;
@@ -1112,10 +1105,7 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
     LaneArgs<T> a;
     carve(h, B, a);
-    const int64_t cmin = h->compact_min_batch < 0
-        ? (h->cfg.max_iter > 16 ? h->geo.scaled(kAutoCompactBatch) : 0) : h->compact_min_batch;
-    const bool chunked = early_exit && cmin > 0 && B >= cmin && h->cfg.max_iter > 4;
-    if (early_exit && !chunked) {  // (the single-launch solve: iterate() above)
+    if (early_exit && !chunked(h, B)) {  // (the single-launch solve: iterate() above)
       if (h->opt_reroll < 0) a.reroll = 0;
       if (h->opt_defer < 0) a.defer = 0;
       finish_options(h, B, a);
@@ -1128,17 +1118,10 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
     LaneArgs<T> a;
     carve(h, B, a);
-    bool launched = false;
-    if constexpr (kStageWeights) {
-      if (c.flags) {
-        hipLaunchKernelGGL((k_lane_rollout<T, Sys, true, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
+    with_weights<kStageWeights>(c.flags, [&](auto W) {
+      hipLaunchKernelGGL((k_lane_rollout<T, Sys, W, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
                          (T*)X, (T*)U, (const T*)x_term, (T*)cost);
-        launched = true;
-      }
-    }
-    if (!launched)
-      hipLaunchKernelGGL((k_lane_rollout<T, Sys, false, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
-                         (T*)X, (T*)U, (const T*)x_term, (T*)cost);
+    });
     HIP_TRY(hipGetLastError());
     return I2LQR_OK;
   }
@@ -1148,19 +1131,11 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
     LaneArgs<T> a;
     carve(h, B, a);
-    bool launched = false;
-    if constexpr (kStageWeights) {
-      if (c.flags) {
-        hipLaunchKernelGGL((k_lane_backward<T, Sys, true, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
-                         (const T*)X, (const T*)U, (const T*)x_term, (const T*)lamb,
-                         (const T*)obs, (T*)K, (T*)k);
-        launched = true;
-      }
-    }
-    if (!launched)
-      hipLaunchKernelGGL((k_lane_backward<T, Sys, false, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
-                         (const T*)X, (const T*)U, (const T*)x_term, (const T*)lamb,
-                         (const T*)obs, (T*)K, (T*)k);
+    with_weights<kStageWeights>(c.flags, [&](auto W) {
+      hipLaunchKernelGGL((k_lane_backward<T, Sys, W, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
+                         (const T*)X, (const T*)U, (const T*)x_term, (const T*)lamb, (const T*)obs,
+                         (T*)K, (T*)k);
+    });
     HIP_TRY(hipGetLastError());
     return I2LQR_OK;
   }
@@ -1171,102 +1146,33 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
     LaneArgs<T> a;
     carve(h, B, a);
-    bool launched = false;
-    if constexpr (kStageWeights) {
-      if (c.flags) {
-        hipLaunchKernelGGL((k_lane_forward<T, Sys, true, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
+    with_weights<kStageWeights>(c.flags, [&](auto W) {
+      hipLaunchKernelGGL((k_lane_forward<T, Sys, W, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
                          (const T*)X, (const T*)U, (const T*)x_term, (const T*)K, (const T*)k,
                          (T*)Xn, (T*)Un, (T*)cost_new);
-        launched = true;
-      }
-    }
-    if (!launched)
-      hipLaunchKernelGGL((k_lane_forward<T, Sys, false, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
-                         (const T*)X, (const T*)U, (const T*)x_term, (const T*)K, (const T*)k,
-                         (T*)Xn, (T*)Un, (T*)cost_new);
+    });
     HIP_TRY(hipGetLastError());
     return I2LQR_OK;
   }
 };
 
-// dispatch over (layout, dtype, system)
-#define I2LQR_DISPATCH(h, CALL)                                                               \
-  do {                                                                                        \
-    const int sid_ = (h)->cfg.system_id;                                                      \
-    if ((h)->cfg.layout == I2LQR_LAYOUT_BATCH_MINOR) {                                        \
-      if ((h)->cfg.dtype == I2LQR_F64) {                                                      \
-        if (sid_ == I2LQR_SYS_BICYCLE4)                                                       \
-          return LaneLaunch<double, Bicycle4<double>, false>::CALL;                           \
-        if (sid_ == I2LQR_SYS_BICYCLE6)                                                       \
-          return LaneLaunch<double, Bicycle6<double>, false>::CALL;                           \
-        if (sid_ == I2LQR_SYS_QUAD12)                                                         \
-          return LaneLaunch<double, Quad12<double>, false>::CALL;                             \
-      } else {                                                                                \
-        if (sid_ == I2LQR_SYS_BICYCLE4) return LaneLaunch<float, Bicycle4<float>, false>::CALL; \
-        if (sid_ == I2LQR_SYS_BICYCLE6) return LaneLaunch<float, Bicycle6<float>, false>::CALL; \
-        if (sid_ == I2LQR_SYS_QUAD12) return LaneLaunch<float, Quad12<float>, false>::CALL;     \
-      }                                                                                       \
-      return fail(I2LQR_ERR_UNSUPPORTED, "system %d is not built for the batch-minor layout", \
-                  sid_);                                                                      \
-    }                                                                                         \
-    if ((h)->cfg.layout == I2LQR_LAYOUT_BATCH_TILED) {                                        \
-      if ((h)->cfg.dtype == I2LQR_F64) {                                                      \
-        if (sid_ == I2LQR_SYS_BICYCLE4)                                                       \
-          return LaneLaunch<double, Bicycle4<double>, true>::CALL;                            \
-        if (sid_ == I2LQR_SYS_BICYCLE6)                                                       \
-          return LaneLaunch<double, Bicycle6<double>, true>::CALL;                            \
-        if (sid_ == I2LQR_SYS_QUAD12)                                                         \
-          return LaneLaunch<double, Quad12<double>, true>::CALL;                              \
-      } else {                                                                                \
-        if (sid_ == I2LQR_SYS_BICYCLE4) return LaneLaunch<float, Bicycle4<float>, true>::CALL; \
-        if (sid_ == I2LQR_SYS_BICYCLE6) return LaneLaunch<float, Bicycle6<float>, true>::CALL; \
-        if (sid_ == I2LQR_SYS_QUAD12) return LaneLaunch<float, Quad12<float>, true>::CALL;      \
-      }                                                                                       \
-      return fail(I2LQR_ERR_UNSUPPORTED, "system %d is not built for the batch-tiled layout", \
-                  sid_);                                                                      \
-    }                                                                                         \
-    if ((h)->cfg.dtype == I2LQR_F64) {                                                        \
-      if (sid_ == I2LQR_SYS_BICYCLE4) return Launch<double, Bicycle4<double>>::CALL;          \
-      if (sid_ == I2LQR_SYS_BICYCLE6) return Launch<double, Bicycle6<double>>::CALL;          \
-      if (sid_ == I2LQR_SYS_QUAD12) return Launch<double, Quad12<double>>::CALL;              \
-    } else {                                                                                  \
-      if (sid_ == I2LQR_SYS_BICYCLE4) return Launch<float, Bicycle4<float>>::CALL;            \
-      if (sid_ == I2LQR_SYS_BICYCLE6) return Launch<float, Bicycle6<float>>::CALL;            \
-      if (sid_ == I2LQR_SYS_QUAD12) return Launch<float, Quad12<float>>::CALL;                \
-    }                                                                                         \
-    return fail(I2LQR_ERR_UNSUPPORTED, "system %d / dtype %d not built", sid_,               \
-                (h)->cfg.dtype);                                                              \
-  } while (0)
-
-int prepare_dispatch(i2lqr_handle* h) { I2LQR_DISPATCH(h, prepare(h)); }
-int names_pair_dispatch(i2lqr_handle* h, int64_t B, int early_exit) {
-  I2LQR_DISPATCH(h, names_pair(h, B, early_exit));
-}
-int dispatch_solve_chained(i2lqr_handle* h, int64_t L, int k, void* X, void* U, const void* x_term,
-                           void* lamb, const void* obs, void* cost, void* K, void* kk, int32_t* iters,
-                           int32_t* status, void* stream) {
-  I2LQR_DISPATCH(h, solve_chained(h, L, k, X, U, x_term, lamb, obs, cost, K, kk, iters, status,
-                                  (hipStream_t)stream));
-}
-int dispatch_rollout(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term, void* cost,
-                     void* stream) {
-  I2LQR_DISPATCH(h, rollout(h, B, X, U, x_term, cost, (hipStream_t)stream));
-}
-int dispatch_backward(i2lqr_handle* h, int64_t B, const void* X, const void* U, const void* x_term,
-                      const void* lamb, const void* obs, void* K, void* k, void* stream) {
-  I2LQR_DISPATCH(h, backward(h, B, X, U, x_term, lamb, obs, K, k, (hipStream_t)stream));
-}
-int dispatch_forward(i2lqr_handle* h, int64_t B, const void* X, const void* U, const void* x_term,
-                     const void* K, const void* k, void* X_new, void* U_new, void* cost_new,
-                     void* stream) {
-  I2LQR_DISPATCH(h, forward(h, B, X, U, x_term, K, k, X_new, U_new, cost_new,
-                            (hipStream_t)stream));
+// f(L()) with L the launcher of the handle's layout, precision and plant (validated by i2lqr_create)
+template <class F> int dispatch(const i2lqr_handle* h, F&& f) {
+  return visit_plant(h->cfg, [&](auto t, auto sys) {
+    using T = decltype(t);
+    using Sys = decltype(sys);
+    if (h->cfg.layout == I2LQR_LAYOUT_BATCH_MINOR) return f(LaneLaunch<T, Sys, false>());
+    if (h->cfg.layout == I2LQR_LAYOUT_BATCH_TILED) return f(LaneLaunch<T, Sys, true>());
+    return f(Launch<T, Sys>());
+  });
 }
 int dispatch_iterate(i2lqr_handle* h, int64_t B, int n_iters, int early_exit, void* X, void* U,
                      const void* x_term, void* lamb, const void* obs, void* cost, void* K, void* k,
                      int32_t* iters, int32_t* status, void* stream) {
-  I2LQR_DISPATCH(h, iterate(h, B, n_iters, early_exit, X, U, x_term, lamb, obs, cost, K, k, iters,
-                            status, (hipStream_t)stream));
+  return dispatch(h, [&](auto L) {
+    return L.iterate(h, B, n_iters, early_exit, X, U, x_term, lamb, obs, cost, K, k, iters, status,
+                     (hipStream_t)stream);
+  });
 }
 
 // Live handles: i2lqr_destroy of NULL is a no-op, of a pointer that is not (or no longer) a live
@@ -1654,7 +1560,7 @@ int i2lqr_create(const i2lqr_config* cfg, i2lqr_handle** out) {
     return fail(I2LQR_ERR_LAUNCH, "could not set up the handle's device state: %s",
                 hipGetErrorString(hipGetLastError()));
   }
-  const int rc = prepare_dispatch(h);
+  const int rc = dispatch(h, [&](auto L) { return L.prepare(h); });
   if (rc != I2LQR_OK) {
     (void)hipFree(h->ticket);
     delete h;
@@ -1798,18 +1704,15 @@ int i2lqr_recommended_layout(const i2lqr_config* cfg, int64_t B, int32_t early_e
   if (B < 0) return fail(I2LQR_ERR_INVALID, "negative batch %lld", (long long)B);
   // what the lane layouts cannot run stays problem-major: non-symmetric weights (the kernels keep
   // the upper triangles), and for quad12 (row-block kernel) fp32 WITH stage weights
-  bool lane_ok = true, weights = false;
+  const bool weights = has_stage_weights(*cfg);
+  bool lane_ok = true;
   for (int i = 0; i < cfg->n; i++)
-    for (int j = 0; j < cfg->n; j++) {
-      if (cfg->Q[i * I2LQR_MAX_N + j] != 0.0) weights = true;
+    for (int j = 0; j < cfg->n; j++)
       if (cfg->Q[i * I2LQR_MAX_N + j] != cfg->Q[j * I2LQR_MAX_N + i] ||
           cfg->Qt[i * I2LQR_MAX_N + j] != cfg->Qt[j * I2LQR_MAX_N + i]) lane_ok = false;
-    }
   for (int a = 0; a < cfg->m; a++)
-    for (int b = 0; b < cfg->m; b++) {
-      if (cfg->R[a * I2LQR_MAX_M + b] != 0.0) weights = true;
+    for (int b = 0; b < cfg->m; b++)
       if (cfg->R[a * I2LQR_MAX_M + b] != cfg->R[b * I2LQR_MAX_M + a]) lane_ok = false;
-    }
   int64_t from;
   switch (cfg->system_id) {
     case I2LQR_SYS_BICYCLE4:
@@ -1894,8 +1797,10 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
     if (h->cfg.system_id == I2LQR_SYS_QUAD12) return "k_lane_iterate_rows";
     // the helper-wavefront form (both precisions, with or without stage weights): decided by the
     // launcher's own helpers on scratch arguments (LaneLaunch::names_pair)
-    return names_pair_dispatch(const_cast<i2lqr_handle*>(h), B, early_exit ? 1 : 0) == 1
-               ? "k_lane_iterate_pair" : "k_lane_iterate";
+    const auto pair = [&](auto L) {
+      return L.names_pair(const_cast<i2lqr_handle*>(h), B, early_exit ? 1 : 0);
+    };
+    return dispatch(h, pair) == 1 ? "k_lane_iterate_pair" : "k_lane_iterate";
   }
   switch (select_fused(h, B, early_exit, nullptr)) {
     case K_SPEC: return "k_group_spec";
@@ -1926,7 +1831,10 @@ int i2lqr_rollout(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_te
   if (int rc = check_common(h, B)) return rc;
   if (B == 0) return I2LQR_OK;
   if (!X || !U || !x_term || !cost) return fail(I2LQR_ERR_INVALID, "null buffer");
-  return debug_check(dispatch_rollout(h, B, X, U, x_term, cost, stream), stream);
+  const int rc = dispatch(h, [&](auto L) {
+    return L.rollout(h, B, X, U, x_term, cost, (hipStream_t)stream);
+  });
+  return debug_check(rc, stream);
 }
 
 int i2lqr_backward(i2lqr_handle* h, int64_t B, const void* X, const void* U, const void* x_term,
@@ -1934,7 +1842,10 @@ int i2lqr_backward(i2lqr_handle* h, int64_t B, const void* X, const void* U, con
   if (int rc = check_common(h, B)) return rc;
   if (B == 0) return I2LQR_OK;
   if (!X || !U || !x_term || !lamb || !K || !k) return fail(I2LQR_ERR_INVALID, "null buffer");
-  return debug_check(dispatch_backward(h, B, X, U, x_term, lamb, obs, K, k, stream), stream);
+  const int rc = dispatch(h, [&](auto L) {
+    return L.backward(h, B, X, U, x_term, lamb, obs, K, k, (hipStream_t)stream);
+  });
+  return debug_check(rc, stream);
 }
 
 int i2lqr_forward(i2lqr_handle* h, int64_t B, const void* X, const void* U, const void* x_term,
@@ -1944,8 +1855,10 @@ int i2lqr_forward(i2lqr_handle* h, int64_t B, const void* X, const void* U, cons
   if (B == 0) return I2LQR_OK;
   if (!X || !U || !x_term || !K || !k || !X_new || !U_new || !cost_new)
     return fail(I2LQR_ERR_INVALID, "null buffer");
-  return debug_check(dispatch_forward(h, B, X, U, x_term, K, k, X_new, U_new, cost_new, stream),
-                     stream);
+  const int rc = dispatch(h, [&](auto L) {
+    return L.forward(h, B, X, U, x_term, K, k, X_new, U_new, cost_new, (hipStream_t)stream);
+  });
+  return debug_check(rc, stream);
 }
 
 int i2lqr_iterate(i2lqr_handle* h, int64_t B, int32_t n_iters, void* X, void* U,
@@ -1984,8 +1897,11 @@ int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void
   if (!X || !U || !x_term || !lamb || !cost) return fail(I2LQR_ERR_INVALID, "null buffer");
   if ((K == nullptr) != (k == nullptr))
     return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
-  return debug_check(dispatch_solve_chained(h, chains, chain_len, X, U, x_term, lamb, obs, cost, K, k,
-                                            iters, status, stream), stream);
+  const int rc = dispatch(h, [&](auto L) {
+    return L.solve_chained(h, chains, chain_len, X, U, x_term, lamb, obs, cost, K, k, iters, status,
+                           (hipStream_t)stream);
+  });
+  return debug_check(rc, stream);
 }
 
 int i2lqr_relax_cost(i2lqr_handle* h, int64_t B, const void* X, const void* x_term,

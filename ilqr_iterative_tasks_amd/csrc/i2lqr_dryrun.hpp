@@ -1,7 +1,8 @@
 // Dry-run launches for the host sanitizers.  Compiled in ONLY with
 // -DI2LQR_DRY_RUN (the AddressSanitizer / UBSan build, `make asan`); active only when the environment
 // says I2LQR_DRY_RUN=1.  i2lqr_create then skips the device, and every kernel launch of the
-// library becomes a RECORD — kernel, grid, workgroup size, dynamic LDS — whose pointer arguments
+// library becomes a RECORD — kernel instantiation, grid, workgroup size, dynamic LDS, arguments
+// (tools/dry_run_fuzz.py --trace writes them all) — whose pointer arguments
 // (plain pointers and every pointer field of IterArgs / LaneArgs / LaneSet) must lie inside a range
 // the driver has declared with i2lqr_dry_run(1, base, bytes): the registered workspace and the
 // caller's arrays.  That puts the host code BEHIND a live handle — workspace carving, the chunked
@@ -23,51 +24,76 @@ namespace dry {
 bool on();                                      // I2LQR_DRY_RUN=1 (read once)
 void allow(const void* base, size_t bytes);     // a range kernel pointers may point into
 void reset();                                   // forget ranges, records and violations
-void record(const char* kernel, dim3 grid, dim3 block, size_t lds);
-void ptr(const char* kernel, const char* field, const void* p);
+// One record per launch: record() opens it with the kernel's instantiation (dladdr on its handle,
+// demangled; `expr`, the launch's spelling, where no exported symbol sits at that address), ptr()
+// and val() append the arguments, end() files it.  A pointer is written as the declared range it
+// lies in plus an offset (r<index>+<bytes>), so two builds of the library give identical records.
+void record(const char* expr, const void* kernel, dim3 grid, dim3 block, size_t lds);
+void ptr(const char* field, const void* p);
+void val(const char* field, int64_t v);
+void end();
 int64_t report(char* buf, int64_t n);           // text of records + violations; returns #violations
 
-template <class A> inline void arg(const char*, const A&) {}  // scalars, device configs
-template <class P> inline void arg(const char* k, P* p) { ptr(k, "pointer argument", (const void*)p); }
-template <class T> inline void arg(const char* k, const IterArgs<T>& a) {
-  ptr(k, "IterArgs.X", a.X); ptr(k, "IterArgs.U", a.U); ptr(k, "IterArgs.x_term", a.x_term);
-  ptr(k, "IterArgs.lamb", a.lamb); ptr(k, "IterArgs.obs", a.obs); ptr(k, "IterArgs.cost", a.cost);
-  ptr(k, "IterArgs.K", a.K); ptr(k, "IterArgs.k", a.k); ptr(k, "IterArgs.iters", a.iters);
-  ptr(k, "IterArgs.status", a.status); ptr(k, "IterArgs.count", a.count);
-  ptr(k, "IterArgs.orig", a.orig); ptr(k, "IterArgs.out_X", a.out_X);
-  ptr(k, "IterArgs.out_U", a.out_U); ptr(k, "IterArgs.out_K", a.out_K);
-  ptr(k, "IterArgs.out_k", a.out_k); ptr(k, "IterArgs.out_lamb", a.out_lamb);
-  ptr(k, "IterArgs.out_cost", a.out_cost); ptr(k, "IterArgs.out_iters", a.out_iters);
-  ptr(k, "IterArgs.out_status", a.out_status); ptr(k, "IterArgs.qfun", a.qfun);
-  ptr(k, "IterArgs.cost_it", a.cost_it); ptr(k, "IterArgs.pick_part", a.pick_part);
-  ptr(k, "IterArgs.pick_ticket", a.pick_ticket); ptr(k, "IterArgs.best_idx", a.best_idx);
-  ptr(k, "IterArgs.best_cost", a.best_cost);
+template <class A> inline void arg(const A&) {}  // device configs
+inline void arg(int64_t v) { val("int", v); }
+inline void arg(int v) { val("int", v); }
+template <class P> inline void arg(P* p) { ptr("pointer argument", (const void*)p); }
+template <class T> inline void arg(const IterArgs<T>& a) {
+  val("IterArgs.B", a.B); val("IterArgs.n_iters", a.n_iters); val("IterArgs.early_exit", a.early_exit);
+  ptr("IterArgs.X", a.X); ptr("IterArgs.U", a.U); ptr("IterArgs.x_term", a.x_term);
+  ptr("IterArgs.lamb", a.lamb); ptr("IterArgs.obs", a.obs); ptr("IterArgs.cost", a.cost);
+  ptr("IterArgs.K", a.K); ptr("IterArgs.k", a.k); ptr("IterArgs.iters", a.iters);
+  ptr("IterArgs.status", a.status); ptr("IterArgs.dbg", a.dbg); ptr("IterArgs.count", a.count);
+  val("IterArgs.count_max", a.count_max); val("IterArgs.max_total", a.max_total);
+  val("IterArgs.set_stride", a.set_stride);
+  ptr("IterArgs.orig", a.orig); ptr("IterArgs.out_X", a.out_X);
+  ptr("IterArgs.out_U", a.out_U); ptr("IterArgs.out_K", a.out_K);
+  ptr("IterArgs.out_k", a.out_k); ptr("IterArgs.out_lamb", a.out_lamb);
+  ptr("IterArgs.out_cost", a.out_cost); ptr("IterArgs.out_iters", a.out_iters);
+  ptr("IterArgs.out_status", a.out_status);
+  val("IterArgs.out_B", a.out_B); val("IterArgs.out_tiled", a.out_tiled);
+  ptr("IterArgs.qfun", a.qfun);
+  val("IterArgs.outer_iter", a.outer_iter); val("IterArgs.max_relax_iter", a.max_relax_iter);
+  ptr("IterArgs.cost_it", a.cost_it); ptr("IterArgs.pick_part", a.pick_part);
+  ptr("IterArgs.pick_ticket", a.pick_ticket); ptr("IterArgs.best_idx", a.best_idx);
+  ptr("IterArgs.best_cost", a.best_cost); val("IterArgs.chain_len", a.chain_len);
 }
 #ifdef I2LQR_DRY_RUN_LANE  // (translation units that see i2lqr_lane.hpp)
-template <class T> inline void arg(const char* k, const LaneSet<T>& s) {
-  ptr(k, "LaneSet.X", s.X); ptr(k, "LaneSet.U", s.U); ptr(k, "LaneSet.x_term", s.x_term);
-  ptr(k, "LaneSet.obs", s.obs); ptr(k, "LaneSet.lamb", s.lamb); ptr(k, "LaneSet.cost", s.cost);
-  ptr(k, "LaneSet.K", s.K); ptr(k, "LaneSet.k", s.k); ptr(k, "LaneSet.iters", s.iters);
-  ptr(k, "LaneSet.status", s.status); ptr(k, "LaneSet.orig", s.orig);
+template <class T> inline void arg(const LaneSet<T>& s) {
+  ptr("LaneSet.X", s.X); ptr("LaneSet.U", s.U); ptr("LaneSet.x_term", s.x_term);
+  ptr("LaneSet.obs", s.obs); ptr("LaneSet.lamb", s.lamb); ptr("LaneSet.cost", s.cost);
+  ptr("LaneSet.K", s.K); ptr("LaneSet.k", s.k); ptr("LaneSet.iters", s.iters);
+  ptr("LaneSet.status", s.status); ptr("LaneSet.orig", s.orig); val("LaneSet.B", s.B);
 }
-template <class T> inline void arg(const char* k, const LaneArgs<T>& a) {
-  ptr(k, "LaneArgs.X", a.X); ptr(k, "LaneArgs.U", a.U); ptr(k, "LaneArgs.x_term", a.x_term);
-  ptr(k, "LaneArgs.lamb", a.lamb); ptr(k, "LaneArgs.obs", a.obs); ptr(k, "LaneArgs.cost", a.cost);
-  ptr(k, "LaneArgs.K", a.K); ptr(k, "LaneArgs.k", a.k); ptr(k, "LaneArgs.iters", a.iters);
-  ptr(k, "LaneArgs.status", a.status); ptr(k, "LaneArgs.wsU", a.wsU); ptr(k, "LaneArgs.wsK", a.wsK);
-  ptr(k, "LaneArgs.wsk", a.wsk); ptr(k, "LaneArgs.wsX", a.wsX); ptr(k, "LaneArgs.count", a.count);
+template <class T> inline void arg(const LaneArgs<T>& a) {
+  val("LaneArgs.B", a.B); val("LaneArgs.n_iters", a.n_iters); val("LaneArgs.early_exit", a.early_exit);
+  ptr("LaneArgs.X", a.X); ptr("LaneArgs.U", a.U); ptr("LaneArgs.x_term", a.x_term);
+  ptr("LaneArgs.lamb", a.lamb); ptr("LaneArgs.obs", a.obs); ptr("LaneArgs.cost", a.cost);
+  ptr("LaneArgs.K", a.K); ptr("LaneArgs.k", a.k); ptr("LaneArgs.iters", a.iters);
+  ptr("LaneArgs.status", a.status); ptr("LaneArgs.wsU", a.wsU); ptr("LaneArgs.wsK", a.wsK);
+  ptr("LaneArgs.wsk", a.wsk); ptr("LaneArgs.wsX", a.wsX); ptr("LaneArgs.count", a.count);
+  val("LaneArgs.resume", a.resume); val("LaneArgs.max_total", a.max_total);
+  val("LaneArgs.count_lo", a.count_lo); val("LaneArgs.count_hi", a.count_hi);
+  val("LaneArgs.two_max", a.two_max); val("LaneArgs.lds_grow", a.lds_grow);
+  ptr("LaneArgs.dbg", a.dbg); val("LaneArgs.defer", a.defer);
+  val("LaneArgs.lds_steps", a.lds_steps); val("LaneArgs.reroll", a.reroll);
+  val("LaneArgs.merge", a.merge); val("LaneArgs.ckpt", a.ckpt); val("LaneArgs.stagger", a.stagger);
+  val("LaneArgs.cp.on", a.cp.on);
   if (a.cp.on) {
-    ptr(k, "LaneArgs.cp.orig", a.cp.orig); ptr(k, "LaneArgs.cp.count_out", a.cp.count_out);
-    arg(k, a.cp.dst);
-    arg(k, a.cp.usr);
+    val("LaneArgs.cp.src_is_user", a.cp.src_is_user); val("LaneArgs.cp.user_tiled", a.cp.user_tiled);
+    ptr("LaneArgs.cp.orig", a.cp.orig); ptr("LaneArgs.cp.count_out", a.cp.count_out);
+    arg(a.cp.dst);
+    arg(a.cp.usr);
   }
 }
 #endif
 
 template <class... A>
-inline void launch(const char* kernel, dim3 grid, dim3 block, size_t lds, const A&... a) {
-  record(kernel, grid, block, lds);
-  (arg(kernel, a), ...);
+inline void launch(const char* expr, const void* kernel, dim3 grid, dim3 block, size_t lds,
+                   const A&... a) {
+  record(expr, kernel, grid, block, lds);
+  (arg(a), ...);
+  end();
 }
 
 }  // namespace dry
@@ -78,7 +104,7 @@ inline void launch(const char* kernel, dim3 grid, dim3 block, size_t lds, const 
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...)                                  \
   do {                                                                                             \
     if (::i2lqr::dry::on())                                                                        \
-      ::i2lqr::dry::launch(#kernel, dim3(grid), dim3(block), (size_t)(lds), __VA_ARGS__);          \
+      ::i2lqr::dry::launch(#kernel, (const void*)(kernel), dim3(grid), dim3(block), (size_t)(lds), __VA_ARGS__);          \
     else                                                                                           \
       hipLaunchKernelGGLInternal((kernel), (grid), (block), (lds), (stream), __VA_ARGS__);         \
   } while (0)

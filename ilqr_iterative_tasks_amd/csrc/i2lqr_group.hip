@@ -14,16 +14,6 @@ template <class T, class Sys, int G = kGroup> size_t group_lds_bytes(int N) {
   return (size_t)GLayout<Sys, G>(N).wave_words() * sizeof(T);
 }
 
-bool has_stage_weights(const i2lqr_config& cfg) {
-  for (int i = 0; i < cfg.n; i++)
-    for (int j = 0; j < cfg.n; j++)
-      if (cfg.Q[i * I2LQR_MAX_N + j] != 0.0) return true;
-  for (int a = 0; a < cfg.m; a++)
-    for (int b = 0; b < cfg.m; b++)
-      if (cfg.R[a * I2LQR_MAX_M + b] != 0.0) return true;
-  return false;
-}
-
 // Launches with more than 64 KiB of dynamic LDS need the kernel's attribute raised — per kernel
 // AND per device (a second GPU used from the same thread has its own copy of the attribute):
 // once per (kernel, device, size).
@@ -129,25 +119,30 @@ hipError_t launch_spec(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_
 }
 template <class T, bool SETIO>
 hipError_t launch_spec_any(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s, int lanes) {
-  const bool b4 = cfg.system_id == I2LQR_SYS_BICYCLE4;
-  if (lanes == 16)
-    return b4 ? launch_spec<T, Bicycle4<T>, SETIO, 16>(cfg, a, s)
-              : launch_spec<T, Bicycle6<T>, SETIO, 16>(cfg, a, s);
-  return b4 ? launch_spec<T, Bicycle4<T>, SETIO, kGroup>(cfg, a, s)
-            : launch_spec<T, Bicycle6<T>, SETIO, kGroup>(cfg, a, s);
+  return visit_bicycle<T>(cfg, [&](auto, auto sys) {
+    using Sys = decltype(sys);
+    return lanes == 16 ? launch_spec<T, Sys, SETIO, 16>(cfg, a, s)
+                       : launch_spec<T, Sys, SETIO, kGroup>(cfg, a, s);
+  });
 }
 
 template <int G> bool spec_lds_fits(const i2lqr_config& cfg) {  // the two-wavefront form
-  const size_t lds = cfg.dtype == I2LQR_F64
-      ? (cfg.system_id == I2LQR_SYS_BICYCLE4 ? spec_lds_bytes<double, Bicycle4<double>, 2, G>(cfg.N)
-                                             : spec_lds_bytes<double, Bicycle6<double>, 2, G>(cfg.N))
-      : (cfg.system_id == I2LQR_SYS_BICYCLE4 ? spec_lds_bytes<float, Bicycle4<float>, 2, G>(cfg.N)
-                                             : spec_lds_bytes<float, Bicycle6<float>, 2, G>(cfg.N));
+  const size_t lds = visit_bicycle(cfg, [&](auto t, auto sys) {
+    return spec_lds_bytes<decltype(t), decltype(sys), 2, G>(cfg.N);
+  });
   return lds <= device_geometry().max_dyn_lds;
 }
 bool spec_plant_ok(const i2lqr_config& cfg) {
   if (cfg.system_id != I2LQR_SYS_BICYCLE4 && cfg.system_id != I2LQR_SYS_BICYCLE6) return false;
   return !has_stage_weights(cfg);
+}
+// the LDS form of the eight- / sixteen-lane kernel fits: the bicycles, Q = R = 0, problem-major
+template <int G> bool group_lds_fits(const i2lqr_config& cfg) {
+  if (!spec_plant_ok(cfg) || cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR) return false;
+  const size_t lds = visit_bicycle(cfg, [&](auto t, auto sys) {
+    return group_lds_bytes<decltype(t), decltype(sys), G>(cfg.N);
+  });
+  return lds <= device_geometry().max_dyn_lds;
 }
 
 }  // namespace
@@ -177,109 +172,70 @@ bool group_spec_chain_supported(const i2lqr_config& cfg, int64_t chains) {
   if (!spec_plant_ok(cfg) || cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR) return false;
   const DeviceGeometry& geo = device_geometry();
   if (chains > geo.scaled(kSpecWideBatch)) return false;  // three wavefronts per workgroup
-  const size_t lds = cfg.dtype == I2LQR_F64
-      ? (cfg.system_id == I2LQR_SYS_BICYCLE4 ? spec_lds_bytes<double, Bicycle4<double>, 3, 16>(cfg.N)
-                                             : spec_lds_bytes<double, Bicycle6<double>, 3, 16>(cfg.N))
-      : (cfg.system_id == I2LQR_SYS_BICYCLE4 ? spec_lds_bytes<float, Bicycle4<float>, 3, 16>(cfg.N)
-                                             : spec_lds_bytes<float, Bicycle6<float>, 3, 16>(cfg.N));
+  const size_t lds = visit_bicycle(cfg, [&](auto t, auto sys) {
+    return spec_lds_bytes<decltype(t), decltype(sys), 3, 16>(cfg.N);
+  });
   return lds <= geo.max_dyn_lds;
 }
-template <> hipError_t group_spec_chain<double>(const i2lqr_config& cfg, const IterArgs<double>& a,
-                                                hipStream_t s) {
-  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch_spec_chain<double, Bicycle4<double>>(cfg, a, s);
-  return launch_spec_chain<double, Bicycle6<double>>(cfg, a, s);
+template <class T>
+hipError_t group_spec_chain(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s) {
+  return visit_bicycle<T>(cfg, [&](auto, auto sys) {
+    return launch_spec_chain<T, decltype(sys)>(cfg, a, s);
+  });
 }
-template <> hipError_t group_spec_chain<float>(const i2lqr_config& cfg, const IterArgs<float>& a,
-                                               hipStream_t s) {
-  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch_spec_chain<float, Bicycle4<float>>(cfg, a, s);
-  return launch_spec_chain<float, Bicycle6<float>>(cfg, a, s);
+template <class T>
+hipError_t group_spec_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s, int lanes) {
+  return launch_spec_any<T, false>(cfg, a, s, lanes);
 }
-
-template <> hipError_t group_spec_iterate<double>(const i2lqr_config& cfg, const IterArgs<double>& a,
-                                                  hipStream_t s, int lanes) {
-  return launch_spec_any<double, false>(cfg, a, s, lanes);
-}
-template <> hipError_t group_spec_iterate<float>(const i2lqr_config& cfg, const IterArgs<float>& a,
-                                                 hipStream_t s, int lanes) {
-  return launch_spec_any<float, false>(cfg, a, s, lanes);
-}
-template <> hipError_t group_spec_tail<double>(const i2lqr_config& cfg, const IterArgs<double>& a,
-                                               hipStream_t s) {
-  return launch_spec_any<double, true>(cfg, a, s, group_spec_tail_lanes(cfg));
-}
-template <> hipError_t group_spec_tail<float>(const i2lqr_config& cfg, const IterArgs<float>& a,
-                                              hipStream_t s) {
-  return launch_spec_any<float, true>(cfg, a, s, group_spec_tail_lanes(cfg));
+template <class T>
+hipError_t group_spec_tail(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s) {
+  return launch_spec_any<T, true>(cfg, a, s, group_spec_tail_lanes(cfg));
 }
 
-bool group16_supported(const i2lqr_config& cfg) {
-  if (cfg.system_id != I2LQR_SYS_BICYCLE4 && cfg.system_id != I2LQR_SYS_BICYCLE6) return false;
-  if (cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR || has_stage_weights(cfg)) return false;
-  const size_t lds = cfg.dtype == I2LQR_F64
-      ? (cfg.system_id == I2LQR_SYS_BICYCLE4 ? group_lds_bytes<double, Bicycle4<double>, 16>(cfg.N)
-                                             : group_lds_bytes<double, Bicycle6<double>, 16>(cfg.N))
-      : (cfg.system_id == I2LQR_SYS_BICYCLE4 ? group_lds_bytes<float, Bicycle4<float>, 16>(cfg.N)
-                                             : group_lds_bytes<float, Bicycle6<float>, 16>(cfg.N));
-  return lds <= device_geometry().max_dyn_lds;
-}
-template <> hipError_t group16_iterate<double>(const i2lqr_config& cfg, const IterArgs<double>& a,
-                                               hipStream_t s, bool overlap) {
-  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch16<double, Bicycle4<double>>(cfg, a, s, overlap);
-  return launch16<double, Bicycle6<double>>(cfg, a, s, overlap);
-}
-template <> hipError_t group16_iterate<float>(const i2lqr_config& cfg, const IterArgs<float>& a,
-                                              hipStream_t s, bool overlap) {
-  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch16<float, Bicycle4<float>>(cfg, a, s, overlap);
-  return launch16<float, Bicycle6<float>>(cfg, a, s, overlap);
+bool group16_supported(const i2lqr_config& cfg) { return group_lds_fits<16>(cfg); }
+template <class T>
+hipError_t group16_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s, bool overlap) {
+  return visit_bicycle<T>(cfg, [&](auto, auto sys) {
+    return launch16<T, decltype(sys)>(cfg, a, s, overlap);
+  });
 }
 
-bool group_supported(const i2lqr_config& cfg) {
-  if (cfg.system_id != I2LQR_SYS_BICYCLE4 && cfg.system_id != I2LQR_SYS_BICYCLE6) return false;
-  if (cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR || has_stage_weights(cfg)) return false;
-  const size_t lds = cfg.dtype == I2LQR_F64
-      ? (cfg.system_id == I2LQR_SYS_BICYCLE4 ? group_lds_bytes<double, Bicycle4<double>>(cfg.N)
-                                             : group_lds_bytes<double, Bicycle6<double>>(cfg.N))
-      : (cfg.system_id == I2LQR_SYS_BICYCLE4 ? group_lds_bytes<float, Bicycle4<float>>(cfg.N)
-                                             : group_lds_bytes<float, Bicycle6<float>>(cfg.N));
-  return lds <= device_geometry().max_dyn_lds;
-}
+bool group_supported(const i2lqr_config& cfg) { return group_lds_fits<kGroup>(cfg); }
 
 int64_t group_workspace_bytes(const i2lqr_config& cfg, int64_t B) {
   if (!group_supported(cfg) || B <= 0) return 0;
   const int64_t probs = (B + kGroupsPerWave - 1) / kGroupsPerWave * kGroupsPerWave;
-  const int64_t words = cfg.system_id == I2LQR_SYS_BICYCLE4
-      ? GLayout<Bicycle4<double>>(cfg.N, true).ws_words()
-      : GLayout<Bicycle6<double>>(cfg.N, true).ws_words();
-  const size_t lds = cfg.dtype == I2LQR_F64
-      ? (cfg.system_id == I2LQR_SYS_BICYCLE4
-             ? (size_t)GLayout<Bicycle4<double>>(cfg.N, true).wave_words() * 8
-             : (size_t)GLayout<Bicycle6<double>>(cfg.N, true).wave_words() * 8)
-      : (cfg.system_id == I2LQR_SYS_BICYCLE4
-             ? (size_t)GLayout<Bicycle4<float>>(cfg.N, true).wave_words() * 4
-             : (size_t)GLayout<Bicycle6<float>>(cfg.N, true).wave_words() * 4);
+  const int64_t words = visit_bicycle<double>(cfg, [&](auto, auto sys) {
+    return GLayout<decltype(sys)>(cfg.N, true).ws_words();
+  });
+  const size_t lds = visit_bicycle(cfg, [&](auto t, auto sys) {
+    return (size_t)GLayout<decltype(sys)>(cfg.N, true).wave_words() * sizeof(t);
+  });
   if (lds > device_geometry().max_dyn_lds) return 0;
   return probs * words * (cfg.dtype == I2LQR_F64 ? 8 : 4);
 }
-template <> hipError_t group_iterate_ws<double>(const i2lqr_config& cfg, const IterArgs<double>& a,
-                                                void* ws, hipStream_t s) {
-  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch_ws<double, Bicycle4<double>>(cfg, a, ws, s);
-  return launch_ws<double, Bicycle6<double>>(cfg, a, ws, s);
-}
-template <> hipError_t group_iterate_ws<float>(const i2lqr_config& cfg, const IterArgs<float>& a,
-                                               void* ws, hipStream_t s) {
-  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch_ws<float, Bicycle4<float>>(cfg, a, ws, s);
-  return launch_ws<float, Bicycle6<float>>(cfg, a, ws, s);
+template <class T>
+hipError_t group_iterate_ws(const i2lqr_config& cfg, const IterArgs<T>& a, void* ws, hipStream_t s) {
+  return visit_bicycle<T>(cfg, [&](auto, auto sys) {
+    return launch_ws<T, decltype(sys)>(cfg, a, ws, s);
+  });
 }
 
-template <> hipError_t group_iterate<double>(const i2lqr_config& cfg, const IterArgs<double>& a,
-                                             hipStream_t s) {
-  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch<double, Bicycle4<double>>(cfg, a, s);
-  return launch<double, Bicycle6<double>>(cfg, a, s);
+template <class T>
+hipError_t group_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s) {
+  return visit_bicycle<T>(cfg, [&](auto, auto sys) { return launch<T, decltype(sys)>(cfg, a, s); });
 }
-template <> hipError_t group_iterate<float>(const i2lqr_config& cfg, const IterArgs<float>& a,
-                                            hipStream_t s) {
-  if (cfg.system_id == I2LQR_SYS_BICYCLE4) return launch<float, Bicycle4<float>>(cfg, a, s);
-  return launch<float, Bicycle6<float>>(cfg, a, s);
-}
+
+#define I2LQR_GROUP_LAUNCHERS(T)                                                                    \
+  template hipError_t group_iterate<T>(const i2lqr_config&, const IterArgs<T>&, hipStream_t);       \
+  template hipError_t group16_iterate<T>(const i2lqr_config&, const IterArgs<T>&, hipStream_t, bool); \
+  template hipError_t group_iterate_ws<T>(const i2lqr_config&, const IterArgs<T>&, void*,           \
+                                          hipStream_t);                                             \
+  template hipError_t group_spec_iterate<T>(const i2lqr_config&, const IterArgs<T>&, hipStream_t,   \
+                                            int);                                                   \
+  template hipError_t group_spec_chain<T>(const i2lqr_config&, const IterArgs<T>&, hipStream_t);    \
+  template hipError_t group_spec_tail<T>(const i2lqr_config&, const IterArgs<T>&, hipStream_t);
+I2LQR_GROUP_LAUNCHERS(double)
+I2LQR_GROUP_LAUNCHERS(float)
 
 }  // namespace i2lqr

@@ -239,3 +239,29 @@ def test_dry_run_hook_is_inert_in_the_product_library():
     for op in (0, 1, 2, 3):
         assert lib.i2lqr_dry_run(op, None, 0) == -2
     assert b"sanitizer build" in lib.i2lqr_last_error()
+
+
+def test_stage_weights_are_read_from_the_plant_blocks_only():
+    """has_stage_weights (i2lqr_devcfg.hpp) reads the n x n block of Q and the m x m block of R, as
+    the kernels do: a non-zero entry in the padding of the I2LQR_MAX_N x I2LQR_MAX_N array changes
+    no decision.  With the sanitizer build the launchers behind a live dry-run handle are checked
+    too (tools/dry_run_fuzz.py: same records, fp64 state checkpoints kept)."""
+    lib = _abi.load_library()
+    for system in ("bicycle4", "bicycle6"):
+        for dtype in ("f64", "f32"):
+            cfg = _abi.default_config(system, 20, dtype)
+            padded = cfg.copy()
+            padded.Q[_abi.MAX_N * _abi.MAX_N - 1] = 1.0
+            for B in (64, 4096, 65536):
+                for early_exit in (0, 1):
+                    assert (lib.i2lqr_recommended_layout(C.byref(padded), B, early_exit)
+                            == lib.i2lqr_recommended_layout(C.byref(cfg), B, early_exit))
+    if "asan" in str(_abi.LIB_PATH):
+        import os
+        import subprocess
+        import sys
+        env = dict(os.environ, I2LQR_DRY_RUN="1")
+        out = subprocess.run([sys.executable, str(ROOT / "tools" / "dry_run_fuzz.py"), "--configs", "0"],
+                             env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout + out.stderr
+        assert "padding of Q changes no launch" in out.stdout

@@ -26,6 +26,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--configs", type=int, default=1000)
 ap.add_argument("--seed", type=int, default=20260406)
 ap.add_argument("--verbose", action="store_true")
+ap.add_argument("--trace", metavar="FILE",
+                help="write every launch record (instantiation, shape, arguments) to FILE: two builds "
+                     "of the library that enqueue the same launches write identical files")
 args = ap.parse_args()
 
 lib = _abi.load_library()
@@ -59,10 +62,17 @@ class Arena:
         return P(base) if nbytes > 0 else P(None)
 
 
-def report():
-    buf = C.create_string_buffer(1 << 16)
+trace = open(args.trace, "w") if args.trace else None
+
+
+def report(label=""):
+    # (the library keeps up to 2 MiB of records between two reports: the trace takes all of them)
+    buf = C.create_string_buffer(1 << 22 if trace else 1 << 16)
     bad = lib.i2lqr_dry_run(3, buf, len(buf))
-    return int(bad), buf.value.decode(errors="replace")
+    text = buf.value.decode(errors="replace")
+    if trace:
+        trace.write(f"# {label}\n{text}")
+    return int(bad), text
 
 
 # The checker must be live: a workspace DECLARED at half the size the library carves it to has to
@@ -82,11 +92,46 @@ for nbytes in (B0 * 6 * 21 * 8, B0 * 2 * 20 * 8, B0 * 6 * 8, B0 * 8, B0 * 8):
     arrs.append(P(a))
 assert lib.i2lqr_solve(h, B0, arrs[0], arrs[1], arrs[2], arrs[3], None, arrs[4], None, None, None, None,
                        STREAM) == 0, lib.i2lqr_last_error()
-bad, text = report()
+bad, text = report("self-check")
 assert bad > 0 and "VIOLATION" in text and "LaneArgs" in text, (bad, text[:400])
 assert lib.i2lqr_destroy(h) == 0
 print(f"self-check: a workspace declared at half its size is reported ({bad} violations, e.g. "
       f"{text.splitlines()[0][:110]})")
+
+
+
+def padding_records(system, dtype, B, pad):
+    """The records of i2lqr_iterate and i2lqr_solve on a batch-minor handle; pad: a non-zero Q
+    entry outside the plant's n x n block, which no kernel reads."""
+    assert lib.i2lqr_dry_run(2, None, 0) == 0
+    cfg = _abi.default_config(system, 20, dtype, dt=0.25, layout=1)
+    if pad:
+        cfg.Q[_abi.MAX_N * _abi.MAX_N - 1] = 1.0
+    h = P()
+    assert lib.i2lqr_create(C.byref(cfg), C.byref(h)) == 0, lib.i2lqr_last_error()
+    item, n, m, N = (8 if dtype == "f64" else 4), cfg.n, cfg.m, cfg.N
+    arena = Arena()
+    X, U = arena.take(B * n * (N + 1) * item), arena.take(B * m * N * item)
+    xt, lamb, cost = arena.take(B * n * item), arena.take(B * item), arena.take(B * item)
+    wsb = int(lib.i2lqr_workspace_bytes(h, B))
+    assert lib.i2lqr_set_workspace(h, arena.take(wsb), wsb) == 0
+    assert lib.i2lqr_iterate(h, B, 5, X, U, xt, lamb, None, cost, None, None, None, None, STREAM) == 0, \
+        lib.i2lqr_last_error()
+    assert lib.i2lqr_solve(h, B, X, U, xt, lamb, None, cost, None, None, None, None, STREAM) == 0, \
+        lib.i2lqr_last_error()
+    bad, text = report(f"padding {system} {dtype} B={B} pad={pad}")
+    assert bad == 0 and text.count("launch ") >= 2, text[:400]
+    assert lib.i2lqr_destroy(h) == 0
+    return text
+
+
+# Stage weights are read from the n x n / m x m blocks only (has_stage_weights): a non-zero entry
+# in the padding of Q changes no launch — fp64 at 65536 problems keeps its state checkpoints.
+for system, dtype in (("bicycle6", "f64"), ("bicycle4", "f32")):
+    plain = padding_records(system, dtype, 65536, False)
+    assert padding_records(system, dtype, 65536, True) == plain
+    assert dtype != "f64" or "LaneArgs.ckpt=1" in plain, plain[:400]
+print("self-check: a non-zero entry in the padding of Q changes no launch")
 
 stats = {"configs": 0, "calls": 0, "ok": 0, "refused": 0, "launches": 0}
 for it in range(args.configs):
@@ -189,7 +234,7 @@ for it in range(args.configs):
         rc = calls[ci]()
         stats["calls"] += 1
         stats["ok" if rc == 0 else "refused"] += 1
-        bad, text = report()
+        bad, text = report(f"configuration {it} call {ci} rc {rc}")
         if bad:
             print(f"VIOLATION in configuration {it}: {system} N={N} {dtype} layout={layout} B={B} "
                   f"call {ci} rc={rc}\n{text}")
@@ -199,6 +244,8 @@ for it in range(args.configs):
             print(it, system, N, dtype, layout, B, "call", ci, "rc", rc, lib.i2lqr_last_error().decode()[:80])
     assert lib.i2lqr_iterate_kernel(h, B) is not None and lib.i2lqr_solve_kernel(h, B) is not None
     assert lib.i2lqr_destroy(h) == 0
+if trace:
+    trace.close()
 print(f"dry-run fuzz: {stats['configs']} configurations, {stats['calls']} calls ({stats['ok']} enqueued, "
       f"{stats['refused']} refused with an error code), {stats['launches']} recorded launches, "
       "0 pointer-range violations")
