@@ -992,8 +992,11 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
         hipLaunchKernelGGL((k_lane_compact<T, TILED>), dim3(cgrid), dim3(256), 0, s, n, m, N, src,
                            src_user ? 1 : 0, count_in, cv.set[cur], count, usr, c.trap);
       const LaneSet<T>& w = cv.set[cur];
-      const bool last_round = final_round > 0 && round + 1 >= final_round;
-      if (wave_tail > 0 && done >= 4) {
+      // the tail kernel runs from 4 iterations on; a final round reached before that is not the
+      // last (its survivors would be left in the work set, unscattered): a later round takes them
+      const bool tail_ran = wave_tail > 0 && done >= 4;
+      const bool last_round = final_round > 0 && round + 1 >= final_round && tail_ran;
+      if (tail_ran) {
         using WL = Launch<T, Sys>;
         const size_t lds_f = WL::fstep_lds_bytes(N);
         IterArgs<T> t = iter_args<T>(B, max_iter, 1, w.X, w.U, w.x_term, w.lamb, w.obs, w.cost, w.K,
@@ -1018,7 +1021,7 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
           }
         }
       }
-      if (last_round && spec_tail) {  // everything has been delivered by the tail kernel
+      if (last_round && spec_tail && tail_ran) {  // the tail kernel has delivered everything
         src_user = true;  // (nothing left to scatter)
         break;
       }

@@ -50,6 +50,116 @@ def dev_batch(solver, host: dict, want_gains=True):
     return buf
 
 
+# per-problem status words (include/i2lqr.h)
+ST_RUNNING, ST_CONVERGED, ST_MAX_ITER, ST_LAMB_OVERFLOW, ST_NONFINITE = 0, 1, 2, 3, 4
+# check_solve_outputs: (X, cost) tolerances of the returned X against the oracle's fp64 rollout of
+# the returned U (per-problem relative, batch_rel_err) and of the returned cost against the
+# rollout's cost (relative to max(|cost|, 1): a target reached to ~0 leaves a cost that is all
+# cancellation).  Measured on the bicycle and quad12 suites: fp64 at most 4e-15 (X) and 6e-14
+# (cost); fp32 at most 9.4e-7 (X) and 1.3e-4 (cost: a terminal error of a few metres computed in
+# fp32 from positions of a few hundred metres keeps about four digits).
+ROLLOUT_TOL = {"f64": (1e-12, 1e-12), "f32": (5e-6, 5e-4)}
+
+
+def check_solve_outputs(solver, cfg, host, buf, early_exit=True, n_iters=None, rollout_bits=True,
+                        chunk=131072):
+    """Checks every problem's outputs of a solve (`early_exit`) or a fixed-count iterate of
+    `n_iters` iterations against what orc_ilqr (oracle/ilqr_oracle.c) can return, without solving:
+
+    - status set: after a solve {CONVERGED, MAX_ITER, LAMB_OVERFLOW}, after a fixed-count iterate
+      {RUNNING, CONVERGED, LAMB_OVERFLOW}; NONFINITE exactly where the returned cost is not finite;
+    - iteration count and status agree: a solve runs 1 ... max_iter iterations, MAX_ITER only at
+      max_iter with lamb <= max_lamb, LAMB_OVERFLOW only with lamb > max_lamb; an iterate runs
+      n_iters everywhere;
+    - lamb history: every iteration multiplies or divides lamb by lamb_factor once, so
+      lamb_out / lamb_in = lamb_factor^j with |j| <= iters and j = iters (mod 2) (log tolerance
+      1e-9 in fp64, 1e-5 in fp32) — a lamb or count taken from another iteration or problem fails;
+    - identity: X[:, :, 0] is the caller's x0 bit for bit, x_term and obs are unchanged (a
+      permutation in compaction, scatter or tail delivery fails);
+    - self-consistency: the oracle's rollout of the returned U from x0 reproduces the returned X and
+      cost to ROLLOUT_TOL, and U lies inside the input box;
+    - descent: a step is accepted only if it lowers the cost, so the returned cost is at most the
+      cost of the caller's (clipped) U (to the cost tolerance of ROLLOUT_TOL).
+
+    `rollout_bits`: the returned X, U and cost also equal solver.rollout of the returned U bit for
+    bit.  Every kernel family steps the plant and sums the cost with the code solver.rollout runs
+    (csrc/i2lqr_systems.hpp), one problem's rollout on one lane, so this holds for the fused
+    iterates, the plain single-launch solves of every family and the lane chunks of the chunked
+    solve, and was measured to hold for its tail kernels too (the speculative eight-lane kernel and
+    the one-problem-per-wavefront kernel: they differ from the lane chunks in the Riccati sums, not
+    in the rollout).  Returns the observed maxima."""
+    import torch
+    from oracle import oracle as orc
+    B = host["X"].shape[0]
+    f64 = solver.dtype == torch.float64
+    npdt = np.float64 if f64 else np.float32
+    x_tol, c_tol = ROLLOUT_TOL["f64" if f64 else "f32"]
+    st = buf["status"].cpu().numpy()
+    it = buf["iters"].cpu().numpy()
+    lamb = buf["lamb"].double().cpu().numpy()
+    cost = buf["cost"].double().cpu().numpy()
+    fin = np.isfinite(cost)
+    assert st.shape == it.shape == lamb.shape == cost.shape == (B,)
+    # status set and iteration counts
+    legal = {ST_CONVERGED, ST_MAX_ITER, ST_LAMB_OVERFLOW} if early_exit else \
+        {ST_RUNNING, ST_CONVERGED, ST_LAMB_OVERFLOW}
+    bad = ~np.isin(st, list(legal)) & fin
+    assert not bad.any(), f"{bad.sum()} problems with status {np.unique(st[bad])} (legal {legal})"
+    assert ((st == ST_NONFINITE) == ~fin).all(), "NONFINITE where the cost is finite, or not set"
+    if early_exit:
+        assert it.min() >= 1 and it.max() <= cfg.max_iter, (it.min(), it.max())
+        mx = st == ST_MAX_ITER
+        assert (it[mx] == cfg.max_iter).all() and (lamb[mx] <= cfg.max_lamb).all()
+        assert (lamb[st == ST_LAMB_OVERFLOW] > cfg.max_lamb).all()
+    else:
+        assert (it == n_iters).all(), np.unique(it)
+    # lamb history
+    lamb_in = np.asarray(host["lamb"], dtype=npdt).astype(np.float64)
+    assert (lamb > 0).all()
+    j = np.log(lamb / lamb_in) / np.log(cfg.lamb_factor)
+    jr = np.rint(j)
+    lamb_err = float(np.abs(j - jr).max() * np.log(cfg.lamb_factor))
+    assert lamb_err <= (1e-9 if f64 else 1e-5), lamb_err
+    assert (np.abs(jr) <= it).all() and ((jr.astype(np.int64) - it) % 2 == 0).all(), \
+        "lamb_out / lamb_in is not lamb_factor^j with |j| <= iters, j = iters (mod 2)"
+    # identity: every problem comes back to its own slot
+    X = to_host(solver, buf["X"])
+    U = to_host(solver, buf["U"])
+    x_term = to_host(solver, buf["x_term"])
+    assert X.dtype == npdt
+    assert np.array_equal(X[:, :, 0], np.asarray(host["X"][:, :, 0], dtype=npdt)), "x0 changed"
+    assert np.array_equal(x_term, np.asarray(host["x_term"], dtype=npdt)), "x_term changed"
+    if buf.get("obs") is not None and host.get("obs") is not None:
+        assert np.array_equal(to_host(solver, buf["obs"]), np.asarray(host["obs"], dtype=npdt))
+    # self-consistency: X and cost are the rollout of U
+    u_max = np.asarray(list(cfg.u_max)[:cfg.m], dtype=npdt)
+    assert (np.abs(U) <= u_max[None, :, None]).all(), "U outside the input box"
+    x_err = c_err = 0.0
+    for lo in range(0, B, chunk):
+        sl = slice(lo, min(B, lo + chunk))
+        f = fin[sl]
+        Xr, Ur, cr = orc.rollout_batch(cfg, X[sl], U[sl], x_term[sl])
+        # inside the box clipping is a no-op (fp32: the box itself is rounded up to fp32 and the
+        # oracle clips to the fp64 box, an input change of at most half an fp32 ulp)
+        assert not f64 or np.array_equal(Ur, U[sl])
+        x_err = max(x_err, batch_rel_err(X[sl][f], Xr[f]))
+        c0 = orc.rollout_batch(cfg, X[sl], np.asarray(host["U"][sl], dtype=npdt), x_term[sl])[2]
+        rise = (cost[sl][f] - c0[f]) / np.maximum(np.abs(c0[f]), 1.0)
+        assert rise.max(initial=0.0) <= c_tol, f"cost above the initial cost: {rise.max():.3e}"
+        c_err = max(c_err, float((np.abs(cost[sl][f] - cr[f]) / np.maximum(np.abs(cr[f]), 1.0))
+                                 .max(initial=0.0)))
+    assert x_err <= x_tol, f"returned X is not the rollout of returned U: {x_err:.3e} > {x_tol}"
+    assert c_err <= c_tol, f"returned cost is not the rollout's cost: {c_err:.3e} > {c_tol}"
+    if rollout_bits:
+        X2, U2 = buf["X"].clone(), buf["U"].clone()
+        c2 = solver.rollout(X2, U2, buf["x_term"])
+        for name, a, b in (("U", U2, buf["U"]), ("X", X2, buf["X"]), ("cost", c2, buf["cost"])):
+            assert torch.equal(a.isnan(), b.isnan()), name
+            assert torch.equal(a.nan_to_num(7.0), b.nan_to_num(7.0)), \
+                f"returned {name} is not bit for bit solver.rollout of returned U"
+    return {"x_err": x_err, "cost_err": c_err, "lamb_err": lamb_err}
+
+
 def problems_from_calls(g, N, n=4, m=2):
     """Golden ilqr() call records (x0, x_term, lamb_in, obs) -> problem-major host batch."""
     B = len(g["x0"])

@@ -5,7 +5,7 @@ forced by set_option("group_overlap", 0): same arithmetic, so every output must 
 import numpy as np
 import pytest
 
-from helpers import dev_batch, to_dev
+from helpers import check_solve_outputs, dev_batch, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -74,6 +74,8 @@ def test_overlap_is_bit_identical_across_batches(torch_mod, system, N, dt, dtype
         host = _batch(cfg, B, 0)
         for how, n_iters in (("iterate", 10), ("solve", None), ("pick", 10)):
             want = _run(solver, host, how, n_iters, 0)
+            if how == "solve":
+                check_solve_outputs(solver, cfg, host, want[0])
             for overlap in (1, -1):
                 _assert_same(torch_mod, _run(solver, host, how, n_iters, overlap), want,
                              (B, how, overlap))
@@ -87,6 +89,8 @@ def test_overlap_is_bit_identical_across_obstacles_and_iterations(torch_mod, obs
     solver, cfg = _solver("bicycle6", 20, "f64", 0.25)
     host = _batch(cfg, 1024, obstacle)
     want = _run(solver, host, how, n_iters, 0)
+    if how == "solve":
+        check_solve_outputs(solver, cfg, host, want[0])
     _assert_same(torch_mod, _run(solver, host, how, n_iters, 1), want, (obstacle, how, n_iters),
                  n_iters)
 

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import batch_rel_err, dev_batch, to_host
+from helpers import batch_rel_err, check_solve_outputs, dev_batch, to_host
 
 pytestmark = pytest.mark.gpu
 
@@ -198,6 +198,7 @@ def test_schedule_options_of_the_chunked_solve_change_no_bit(torch_mod):
     solver.set_compaction(0)
     plain = solver.solve(dev_batch(solver, host, want_gains=False))
     assert int((plain["iters"] > 14).sum()) > 1000
+    check_solve_outputs(solver, cfg, host, plain)
     solver.set_compaction(4096)
     solver.set_option("wave_tail", 0)
     # (round 6: the compaction folded into the chunks' exit or as launches of its own, and the
@@ -208,6 +209,7 @@ def test_schedule_options_of_the_chunked_solve_change_no_bit(torch_mod):
         for key in ("first_chunk", "chunk_step", "fused_compaction", "final_round"):
             solver.set_option(key, opts.get(key, -1))
         got = solver.solve(dev_batch(solver, host, want_gains=False))
+        check_solve_outputs(solver, cfg, host, got)
         for key in ("X", "U", "lamb", "cost", "iters", "status"):
             assert torch.equal(got[key], plain[key]), (opts, key)
 
@@ -222,8 +224,10 @@ def test_default_chunked_solve_on_other_distributions_matches_the_plain_solve(to
     B = 32768
     host = workloads.make_batch(cfg, B, variant=variant)
     chunked = solver.solve(dev_batch(solver, host, want_gains=False))
+    check_solve_outputs(solver, cfg, host, chunked)
     solver.set_compaction(0)
     plain = solver.solve(dev_batch(solver, host, want_gains=False))
+    check_solve_outputs(solver, cfg, host, plain)
     assert torch.equal(chunked["iters"], plain["iters"])
     assert torch.equal(chunked["status"], plain["status"])
     assert batch_rel_err(to_host(solver, chunked["X"]), to_host(solver, plain["X"])) < 1e-8
@@ -425,6 +429,7 @@ def test_survivor_chunks_of_a_large_solve_pick_their_kernel_on_the_device(torch_
             assert s.iterate_kernel(B) == "k_lane_iterate"  # the batch as a whole: one wavefront
             so = s.solve(dev_batch(s, host))
             torch.cuda.synchronize()
+            check_solve_outputs(s, cfg, host, so)
             outs.append(so)
         for key in ("X", "U", "lamb", "cost", "iters", "status"):
             assert torch.equal(outs[0][key], outs[1][key]), (B, variant, key)

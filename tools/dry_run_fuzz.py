@@ -13,6 +13,7 @@ violation, an out-of-bounds host access or undefined behaviour is the sanitizers
 import argparse
 import ctypes as C
 import os
+import re
 import sys
 from pathlib import Path
 
@@ -75,6 +76,76 @@ def report(label=""):
     return int(bad), text
 
 
+FIELD = re.compile(r" ([A-Za-z_][A-Za-z_.]*)=(\S+)")
+
+
+def records(text):
+    """Launch records of a report -> [(kernel, {field: value})]; pointers stay strings."""
+    out = []
+    for line in text.splitlines():
+        if not line.startswith("launch ") or " grid " not in line:
+            continue
+        kernel, rest = line[7:].split(" grid ", 1)
+        out.append((kernel, {k: (int(v) if re.fullmatch(r"-?\d+", v) else v)
+                             for k, v in FIELD.findall(" grid " + rest)}))
+    return out
+
+
+def schedule_gap(text):
+    """The chunked solve must leave no survivor behind: the lane chunks of a solve (LaneArgs with
+    early_exit; the helper-wavefront and plain kernel of one round, enqueued as a pair, count once)
+    sum to max_iter, or the last chunk or tail launch is a tail kernel (IterArgs with a live count)
+    that takes every problem (count_max == B) to max_iter.  Returns a description of the gap, or
+    None (also for calls without a lane solve)."""
+    chunks, last, prev = 0, None, None
+    total = None
+    for kernel, f in records(text):
+        if f.get("LaneArgs.early_exit") == 1:
+            if total is None:
+                total = f["LaneArgs.max_total"]
+            partner = (prev is not None and f["LaneArgs.count_lo"] >= 0
+                       and prev.get("LaneArgs.count_hi") == f["LaneArgs.count_lo"]
+                       and prev.get("LaneArgs.n_iters") == f["LaneArgs.n_iters"])
+            if not partner:
+                chunks += f["LaneArgs.n_iters"]
+            last = ("chunk", f)
+        elif total is not None and f.get("IterArgs.count", 0) != 0 and \
+                f.get("IterArgs.early_exit") == 1:
+            last = ("tail", f)
+        prev = f
+    if total is None or chunks == total:
+        return None
+    if last[0] == "tail" and last[1]["IterArgs.count_max"] == last[1]["IterArgs.B"] and \
+            last[1]["IterArgs.max_total"] == total:
+        return None
+    what = "a lane chunk" if last[0] == "chunk" else \
+        f"a tail kernel with count_max {last[1]['IterArgs.count_max']}"
+    return (f"the lane chunks run {chunks} of {total} iterations and the last launch is {what}: "
+            "survivors are left unsolved")
+
+
+def solve_records(options, B=8192, max_iter=150):
+    """The records of one i2lqr_solve on a batch-tiled bicycle6 handle with `options`."""
+    assert lib.i2lqr_dry_run(2, None, 0) == 0
+    cfg = _abi.default_config("bicycle6", 20, "f64", dt=0.25, layout=2)
+    cfg.max_iter = max_iter
+    h = P()
+    assert lib.i2lqr_create(C.byref(cfg), C.byref(h)) == 0, lib.i2lqr_last_error()
+    for name, v in options.items():
+        assert lib.i2lqr_set_option(h, name.encode(), v) == 0
+    arena = Arena()
+    X, U = arena.take(B * 6 * 21 * 8), arena.take(B * 2 * 20 * 8)
+    xt, lamb, cost = arena.take(B * 6 * 8), arena.take(B * 8), arena.take(B * 8)
+    wsb = int(lib.i2lqr_workspace_bytes(h, B))
+    assert lib.i2lqr_set_workspace(h, arena.take(wsb), wsb) == 0
+    assert lib.i2lqr_solve(h, B, X, U, xt, lamb, None, cost, None, None, None, None, STREAM) == 0, \
+        lib.i2lqr_last_error()
+    bad, text = report(f"schedule {options} B={B} max_iter={max_iter}")
+    assert bad == 0, text[:400]
+    assert lib.i2lqr_destroy(h) == 0
+    return text
+
+
 # The checker must be live: a workspace DECLARED at half the size the library carves it to has to
 # come back as violations (the second work set of the chunked solve lies behind the declared half).
 cfg = _abi.default_config("bicycle6", 20, "f64", dt=0.25, layout=2)
@@ -133,7 +204,17 @@ for system, dtype in (("bicycle6", "f64"), ("bicycle4", "f32")):
     assert dtype != "f64" or "LaneArgs.ckpt=1" in plain, plain[:400]
 print("self-check: a non-zero entry in the padding of Q changes no launch")
 
-stats = {"configs": 0, "calls": 0, "ok": 0, "refused": 0, "launches": 0}
+# Every survivor of the chunked solve is covered: the automatic schedule, and the schedules whose
+# final round comes before the tail kernel may run (4 iterations)
+for opts in ({}, {"first_chunk": 2, "final_round": 1},
+             {"first_chunk": 1, "chunk_step": 1, "final_round": 2},
+             {"first_chunk": 3, "final_round": 1, "fused_compaction": 0}):
+    gap = schedule_gap(solve_records(opts))
+    assert gap is None, f"chunked solve with {opts}: {gap}"
+print("self-check: the chunked solve's schedules cover every survivor (automatic; final round "
+      "before 4 iterations)")
+
+stats = {"configs": 0, "calls": 0, "ok": 0, "refused": 0, "launches": 0, "schedules": 0}
 for it in range(args.configs):
     system = rng.choice(["bicycle4", "bicycle6", "quad12"], p=[0.35, 0.45, 0.2])
     N = int(rng.choice([2, 3, 6, 10, 20, 31, 50, 64]))
@@ -239,6 +320,12 @@ for it in range(args.configs):
             print(f"VIOLATION in configuration {it}: {system} N={N} {dtype} layout={layout} B={B} "
                   f"call {ci} rc={rc}\n{text}")
             sys.exit(1)
+        gap = schedule_gap(text) if rc == 0 else None
+        if gap:
+            print(f"SCHEDULE GAP in configuration {it}: {system} N={N} {dtype} layout={layout} "
+                  f"B={B} call {ci}: {gap}\n{text}")
+            sys.exit(1)
+        stats["schedules"] += text.count("LaneArgs.early_exit=1") > 0
         stats["launches"] += text.count("\n")
         if args.verbose:
             print(it, system, N, dtype, layout, B, "call", ci, "rc", rc, lib.i2lqr_last_error().decode()[:80])
@@ -248,4 +335,5 @@ if trace:
     trace.close()
 print(f"dry-run fuzz: {stats['configs']} configurations, {stats['calls']} calls ({stats['ok']} enqueued, "
       f"{stats['refused']} refused with an error code), {stats['launches']} recorded launches, "
-      "0 pointer-range violations")
+      f"0 pointer-range violations, {stats['schedules']} lane solves whose schedule covers every "
+      "survivor")
