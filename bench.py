@@ -27,9 +27,17 @@ inputs are seeded, so two builds run with the same arguments can be compared arr
 Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel against the HBM peak with the
 ALGORITHMIC bytes of SURVEY.md §8(d) (4968 B per iteration per problem at n=6, m=2, N=20, fp64);
 `roofline_issue` prices the same kernel against the instruction-issue peak of its wavefronts (the
-bound that matters while a launch is one wavefront per SIMD); `cpu_baseline` times the CPU oracle
-(a port, oracle/ilqr_oracle.c) on the host cores of the same box on a bounded sample of the same
-workload.
+bound that matters while a launch is one wavefront per SIMD); `cpu_baseline` (--full) times the CPU
+oracle (a port, oracle/ilqr_oracle.c) on the host cores of the same box on a bounded sample of the
+same workload.
+
+A plain run does what its headline figure needs: set-up, warm-up, the timed steps, --dump-outputs
+and the JSON line, whose `roofline` and `roofline_issue` come from event brackets inside the timed
+steps.  --full adds everything that takes runs of its own: `cpu_baseline`, the secondary workloads
+(`extra`, `roofline_large_batch`, `roofline_solve` and their claim scalars in `roofline`) and, with
+--gpus N, the `long_run` and the host-driven and two-collective forms of the round
+(`exchange.phases_ms`, `host_driven_variant`, `broadcast_variant`).  --no-cpu-baseline and
+--no-extra leave parts of that out again.
 
 --exchange-only (no GPU needed; gloo): the multi-rank harness alone — launcher, process group,
 barriers, max-over-ranks timing, all-gather of synthetic cost shards, local arg-min — with the
@@ -80,9 +88,13 @@ def parse_args(argv=None):
                          "fall back on should grouped collectives misbehave on a node)")
     ap.add_argument("--exchange-only", action="store_true",
                     help="CPU/gloo dry run of the multi-rank harness without the solve (see above)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline time budget")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: CPU baseline, secondary workloads and their claim "
+                         "scalars; --gpus N: long run, host-driven and two-collective rounds")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the secondary workloads")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="--full: CPU baseline time budget")
     ap.add_argument("--test-hooks", action="store_true",
                     help="tests only: honour I2LQR_BENCH_TEST_HANG (an attempt that never returns)")
     ap.add_argument("--launch-timeout", type=float, default=900.0,
@@ -615,7 +627,7 @@ def run_gpu(args, cfg, B, rank, world, torch, dist_mod, steps, warmup, with_tail
         # arg-min, round winner; what round 5 timed) on fresh copies of the batch: the phase marks
         # of the exchange come from here, and its ms_per_step beside the one-call form's is what
         # the C entry point buys on this box.
-        if B <= 65536 and args.handoff == "gather":
+        if args.full and B <= 65536 and args.handoff == "gather":
             fresh_sets()
             h_seconds = timed_loop("gather_host")
             res["exchange_ms"] = ms("start", "picked")
@@ -626,7 +638,7 @@ def run_gpu(args, cfg, B, rank, world, torch, dist_mod, steps, warmup, with_tail
         # The two-collective form for comparison (the pick read back, ONE ncclBroadcast from the
         # owner: i2lqr_broadcast_winner — what the controller's list-of-lists rounds use), on fresh
         # copies of the batch, same steps: its host round trip per step serialises the pipeline.
-        if B <= 65536 and args.handoff == "gather":
+        if args.full and B <= 65536 and args.handoff == "gather":
             fresh_sets()
             b_seconds = timed_loop("broadcast")
             res["broadcast_variant"] = {
@@ -1237,7 +1249,7 @@ def run_rank(args) -> int:
                   "broadcast_variant"):
             if k in res:
                 out["exchange"][k] = res[k]
-    if world > 1 and args.steps < LONG_RUN_STEPS:
+    if args.full and world > 1 and args.steps < LONG_RUN_STEPS:
         # the contract's K timed steps may be a few milliseconds, of which the two barriers are a
         # visible share: the same loop once more over LONG_RUN_STEPS steps, reported beside it
         lr = run_gpu(args, cfg, B, rank, world, torch, dist_mod, LONG_RUN_STEPS, args.warmup,
@@ -1270,10 +1282,11 @@ def run_rank(args) -> int:
     # issuing (any / VALU), parked on s_waitcnt, stalled
     out["roofline_issue"]["sq_shares_of_wave_cycles"] = pmc.get(key, "sq_shares_of_wave_cycles")
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, B, args.iters, args.cpu_seconds)
+    with_extra = args.full and not args.no_extra
     extra = {}
-    if not args.no_extra:
+    if with_extra:
         # configs[3] strong-scaled: 2^20 problems over all ranks, exchange included
         total = 1 << 20
         ecfg = workloads.config_for(args.workload, "f64")
@@ -1286,7 +1299,7 @@ def run_rank(args) -> int:
             "layout": r["layout"], "kernel_ms": r["kernel_ms"], "achieved_GBs_per_gpu": ach,
             "hbm_frac_per_gpu": ach / HBM_PEAK_GBS,
             "exchange_ms_per_step": r.get("exchange_ms"), "nccl_world": r.get("nccl_world")}
-    if world == 1 and not args.no_extra:
+    if world == 1 and with_extra:
         # secondary single-GPU workloads (not the headline): EXTRA_LAUNCHES individually timed
         # launches each after EXTRA_WARMUP, median kernel time (min / max / spread beside it)
         def timed(workload, edt, eb, iters):
@@ -1380,7 +1393,7 @@ def run_rank(args) -> int:
         out["extra"] = extra
     if "dump_outputs" in res:
         out["dump_outputs"] = res["dump_outputs"]
-    if world == 1 and not args.no_extra:
+    if world == 1 and with_extra:
         # The figures that carry the claims, as FLAT scalars of `roofline` IMMEDIATELY behind `frac`
         # (a consumer that keeps the first scalars of `roofline` still finds every
         # one; round 5's sat behind a dict and were cut): the full objects stay where they are.

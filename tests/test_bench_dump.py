@@ -26,6 +26,12 @@ def test_steps_and_dump_arguments():
             bench.parse_args(argv)
 
 
+def test_full_is_off_by_default():
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--full", "--no-extra", "--cpu-seconds", "2"])
+    assert a.full and a.no_extra and not a.no_cpu_baseline and a.cpu_seconds == 2.0
+
+
 def test_small_batch_is_written_whole(tmp_path):
     torch = pytest.importorskip("torch")
     outs = _outs(torch, 1024, torch.float64)

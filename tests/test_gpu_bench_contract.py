@@ -1,5 +1,6 @@
-"""GPU suite: bench.py honours the driver's contract — one JSON line with the BASELINE metric, the
-roofline object of the dominant kernel and the CPU baseline — and __graft_entry__.smoke() passes."""
+"""GPU suite: bench.py honours the driver's contract — one JSON line with the BASELINE metric and the
+roofline object of the dominant kernel; with --full also the CPU baseline and the secondary figures —
+and __graft_entry__.smoke() passes."""
 import json
 import subprocess
 import sys
@@ -13,7 +14,7 @@ ROOT = Path(__file__).resolve().parent.parent
 
 def test_bench_json_line_contract():
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "3", "--warmup", "1",
-                          "--no-extra", "--cpu-seconds", "1"], capture_output=True, text=True,
+                          "--full", "--no-extra", "--cpu-seconds", "1"], capture_output=True, text=True,
                          timeout=600, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -107,7 +108,7 @@ def test_default_bench_line_carries_the_claim_scalars_at_the_head_of_roofline():
     consumer that re-parses the line and keeps only the first 32 SCALAR keys of `roofline` (the six
     mandated keys + the claims) still finds every one."""
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "20", "--warmup", "5",
-                          "--cpu-seconds", "1"], capture_output=True, text=True, timeout=1200,
+                          "--full", "--cpu-seconds", "1"], capture_output=True, text=True, timeout=1200,
                          cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -151,6 +152,26 @@ def test_default_bench_line_carries_the_claim_scalars_at_the_head_of_roofline():
     assert cl["reference"]["control_step_ms_mean"] == 700.0
 
 
+def test_plain_bench_line_is_the_headline_alone():
+    """Without --full the run sets up, warms up, times its steps and prints the line: the headline
+    and the roofline of the timed kernel, and nothing that takes runs of its own."""
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "20", "--warmup", "5"],
+                         capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("batched iLQR iterations/s") and d["unit"] == "iLQR iterations/s"
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["dtype"] == "f64"
+    assert d["higher_is_better"] is True and d["value"] > 1e6
+    assert abs(d["value"] - 1024 * 10 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for key in ("cpu_baseline", "extra", "roofline_large_batch", "roofline_solve", "long_run"):
+        assert key not in d, key
+    r = d["roofline"]
+    assert r["kernel"] == "k_group_iterate (sixteen lanes)" and r["kernel_ms_samples"] == 10
+    assert r["kernel_ms_avg"] <= d["ms_per_step"] and not set(CLAIMS) & set(r)
+
+
 def test_bench_under_torchrun_world_of_one_uses_the_native_rccl_exchange():
     """The driver's N > 1 command form with one rank (all this box has): RCCL process group,
     communicator created through the C-ABI, i2lqr_allgather_costs on the side stream, pick checked
@@ -162,7 +183,7 @@ def test_bench_under_torchrun_world_of_one_uses_the_native_rccl_exchange():
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                           "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port",
                           str(port), str(ROOT / "bench.py"), "--gpus", "1", "--steps", "5",
-                          "--warmup", "2", "--no-cpu-baseline"],
+                          "--warmup", "2", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -213,7 +234,8 @@ def test_two_ranks_sharing_the_gpu_solve_their_shards_and_fall_back_together():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "6",
-                          "--warmup", "2", "--no-extra", "--no-cpu-baseline", "--launch-timeout", "240"],
+                          "--warmup", "2", "--full", "--no-extra", "--no-cpu-baseline",
+                          "--launch-timeout", "240"],
                          capture_output=True, text=True, timeout=900, cwd=str(ROOT), env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -273,7 +295,8 @@ def test_two_gpus_native_rccl_round_hands_over_the_owners_trajectory(handoff):
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two HIP devices")
     out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "5",
-                          "--warmup", "2", "--no-cpu-baseline", "--no-extra", "--handoff", handoff],
+                          "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extra",
+                          "--handoff", handoff],
                          capture_output=True, text=True, timeout=1200, cwd=str(ROOT))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]

@@ -67,7 +67,7 @@ done
 cd "$ROOT"
 python3 tools/summarise_profiles.py "$RAW" "$NEW" "$TAG" > "$NEW/summarise.log" 2>&1
 cp "$NEW/pmc_traffic.json" "$ROOT/profiles/pmc_traffic.json"   # bench.py reads it from profiles/
-python3 bench.py 2> "$NEW/bench.err" | grep '^{"metric"' | tail -1 > "$NEW/${TAG}_bench.json"
+python3 bench.py --full 2> "$NEW/bench.err" | grep '^{"metric"' | tail -1 > "$NEW/${TAG}_bench.json"
 python3 tools/extract_bench_profiles.py "$NEW/${TAG}_bench.json" "$TAG" "$NEW"
 # one solve of 65536 problems as a timeline of dispatches (tools/solve_timeline.py)
 cd /tmp

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Split a bench.py JSON line into the per-claim files under profiles/ (VERDICT r5 #1, #2, #6):
+"""Split a `bench.py --full` JSON line into the per-claim files under profiles/ (VERDICT r5 #1, #2, #6):
     <tag>_bench.json               the whole line
     <tag>_sharded_overhead.json    per-rank cost of the sharded step beside the unsharded one
     <tag>_controller_latency.json  BASELINE configs[0] through control.iLqr: control-step latency
@@ -13,7 +13,7 @@ src, tag = Path(sys.argv[1]), sys.argv[2]
 out = Path(sys.argv[3]) if len(sys.argv) > 3 else src.parent
 line = [l for l in src.read_text().splitlines() if l.startswith('{"metric"')][-1]
 d = json.loads(line)
-stamp = {"library_sha256": d["roofline"].get("library_sha256"), "source": f"{tag}_bench.json (python bench.py)"}
+stamp = {"library_sha256": d["roofline"].get("library_sha256"), "source": f"{tag}_bench.json (python bench.py --full)"}
 (out / f"{tag}_bench.json").write_text(line + "\n")
 ex = d.get("extra", {})
 if "sharded_overhead" in ex:
