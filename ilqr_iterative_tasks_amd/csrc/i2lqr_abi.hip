@@ -291,6 +291,7 @@ struct i2lqr_handle {
   int opt_spec;   // eight-lane kernel: speculative form (2-3 wavefronts per eight problems); -1 = automatic
   int opt_group_ws;  // eight-lane kernel: workspace form (records / gains in HBM); -1 = automatic
   int opt_group_overlap;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; -1 = automatic (on)
+  int opt_group_fixed;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; -1 = automatic (on)
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
   // it into its kernel, otherwise the call runs the separate kernels.  The pointer to the call's
   // epilogue is THREAD-LOCAL (t_epi below), not handle state: two host threads inside
@@ -525,7 +526,8 @@ template <class T, class Sys> struct Launch {
         break;
       case K_GROUP16:
         if constexpr (m == 2 && n + m <= 8) {
-          HIP_TRY(group16_iterate<T>(h->cfg, a, s, h->opt_group_overlap != 0));
+          HIP_TRY(group16_iterate<T>(h->cfg, a, s, h->opt_group_overlap != 0,
+                                     h->opt_group_fixed != 0));
           return I2LQR_OK;
         }
         break;
@@ -1536,6 +1538,7 @@ int i2lqr_create(const i2lqr_config* cfg, i2lqr_handle** out) {
   h->opt_defer = h->opt_reroll = h->opt_lds_steps = h->opt_fstep = h->opt_group = -1;
   h->opt_merge = h->opt_ckpt = h->opt_spec = h->opt_stagger = h->opt_group_ws = -1;
   h->opt_group_overlap = -1;
+  h->opt_group_fixed = -1;
   h->wave_tail = -1;
   h->opt_first_chunk = -1;
   h->opt_fuse = -1;
@@ -1769,6 +1772,7 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   else if (!strcmp(name, "speculate")) h->opt_spec = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "group_workspace")) h->opt_group_ws = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "group_overlap")) h->opt_group_overlap = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "group_fixed_horizon")) h->opt_group_fixed = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "debug_self_test")) {
     // Debug build only: provoke one index violation on purpose (a Slice of 8 words indexed at 8)
     // and return what the next call would: I2LQR_ERR_LAUNCH with the decoded record.

@@ -23,8 +23,19 @@ template <class T> hipError_t group_iterate(const i2lqr_config& cfg, const IterA
 constexpr int64_t kGroup16Batch = 4096;
 bool group16_supported(const i2lqr_config& cfg);
 // overlap = false: the one-helper schedule wherever the launcher would pick the overlapped one
+// fixed = false: the run-time-horizon kernel even where the fixed-horizon one is built
 template <class T> hipError_t group16_iterate(const i2lqr_config& cfg, const IterArgs<T>& a,
-                                              hipStream_t stream, bool overlap = true);
+                                              hipStream_t stream, bool overlap = true,
+                                              bool fixed = true);
+// Fixed-horizon form of the sixteen-lane kernel (k_group_iterate_fixed: the horizon a compile-time
+// constant, the fast passes straight-line code), compiled in i2lqr_group_fixed.hip for the horizons
+// of this list — THE list: instantiations and dispatch both expand it.  20 is the horizon of the
+// BASELINE configs 2-4.  Each entry is twelve kernels (two plants, two precisions, H = 1, 2, 3).
+#define I2LQR_GROUP_FIXED_HORIZONS(X) X(20)
+bool group16_fixed_horizon(int N);
+// wavefronts: 1, 2 or 3 per workgroup, as group16_iterate chose them; N must be in the list
+template <class T> hipError_t group16_iterate_fixed(const i2lqr_config& cfg, const IterArgs<T>& a,
+                                                    hipStream_t stream, int wavefronts);
 
 // Workspace form of the same kernel (records and gains in a caller-provided HBM workspace of
 // group_workspace_bytes() for B problems: 4 KB of LDS per problem, four wavefronts per CU): the

@@ -5,33 +5,11 @@
 #include "i2lqr_geometry.hpp"
 #include "i2lqr_group.hpp"
 #include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
+#include "i2lqr_group_launch.hpp"
 
 namespace i2lqr {
 
 namespace {
-
-template <class T, class Sys, int G = kGroup> size_t group_lds_bytes(int N) {
-  return (size_t)GLayout<Sys, G>(N).wave_words() * sizeof(T);
-}
-
-// Launches with more than 64 KiB of dynamic LDS need the kernel's attribute raised — per kernel
-// AND per device (a second GPU used from the same thread has its own copy of the attribute):
-// once per (kernel, device, size).
-template <auto Kernel> hipError_t raise_lds_limit(size_t lds) {
-  if (lds <= device_geometry().default_dyn_lds) return hipSuccess;
-  constexpr int kMaxDev = 64;
-  static thread_local int raised_for[kMaxDev] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= kMaxDev || raised_for[dev] < (int)lds) {
-    e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < kMaxDev) raised_for[dev] = (int)lds;
-  }
-  return hipSuccess;
-}
 
 template <class T, class Sys, int H, int G = kGroup>
 hipError_t launch_h(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s) {
@@ -52,13 +30,20 @@ hipError_t launch_h(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s
 // 3, false, 16>; overlap = false forces the one-helper form): two helpers take all the records
 // while the main wavefront computes the terminal block, and they store the gains at exit — while
 // every workgroup has a CU to itself (<= 256 workgroups = 1024 problems: three SIMDs of four).
+// fixed: the fixed-horizon kernel (k_group_iterate_fixed, i2lqr_group_fixed.hip) with the same number
+// of wavefronts, where the horizon is one it is built for; no effect for any other horizon.
 template <class T, class Sys>
-hipError_t launch16(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s, bool overlap) {
+hipError_t launch16(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s, bool overlap,
+                    bool fixed) {
   const int64_t cus = device_geometry().cus;
+  int wavefronts = 1;
 #ifndef I2LQR_STAMPS
-  if (overlap && (a.B + 3) / 4 <= cus) return launch_h<T, Sys, 3, 16>(cfg, a, s);
-  if ((a.B + 3) / 4 <= 2 * cus) return launch_h<T, Sys, 2, 16>(cfg, a, s);
+  if (overlap && (a.B + 3) / 4 <= cus) wavefronts = 3;
+  else if ((a.B + 3) / 4 <= 2 * cus) wavefronts = 2;
+  if (fixed && group16_fixed_horizon(cfg.N)) return group16_iterate_fixed<T>(cfg, a, s, wavefronts);
 #endif
+  if (wavefronts == 3) return launch_h<T, Sys, 3, 16>(cfg, a, s);
+  if (wavefronts == 2) return launch_h<T, Sys, 2, 16>(cfg, a, s);
   return launch_h<T, Sys, 1, 16>(cfg, a, s);
 }
 // Two helper wavefronts for the record phase (k_group_iterate<.., 3>) while every workgroup has
@@ -194,9 +179,10 @@ hipError_t group_spec_tail(const i2lqr_config& cfg, const IterArgs<T>& a, hipStr
 
 bool group16_supported(const i2lqr_config& cfg) { return group_lds_fits<16>(cfg); }
 template <class T>
-hipError_t group16_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s, bool overlap) {
+hipError_t group16_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, hipStream_t s, bool overlap,
+                           bool fixed) {
   return visit_bicycle<T>(cfg, [&](auto, auto sys) {
-    return launch16<T, decltype(sys)>(cfg, a, s, overlap);
+    return launch16<T, decltype(sys)>(cfg, a, s, overlap, fixed);
   });
 }
 
@@ -228,7 +214,8 @@ hipError_t group_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, hipStrea
 
 #define I2LQR_GROUP_LAUNCHERS(T)                                                                    \
   template hipError_t group_iterate<T>(const i2lqr_config&, const IterArgs<T>&, hipStream_t);       \
-  template hipError_t group16_iterate<T>(const i2lqr_config&, const IterArgs<T>&, hipStream_t, bool); \
+  template hipError_t group16_iterate<T>(const i2lqr_config&, const IterArgs<T>&, hipStream_t, bool, \
+                                         bool);                                                    \
   template hipError_t group_iterate_ws<T>(const i2lqr_config&, const IterArgs<T>&, void*,           \
                                           hipStream_t);                                             \
   template hipError_t group_spec_iterate<T>(const i2lqr_config&, const IterArgs<T>&, hipStream_t,   \

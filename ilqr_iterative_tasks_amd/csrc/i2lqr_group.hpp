@@ -187,13 +187,20 @@ template <class T, int R> __device__ __forceinline__ void dpp_ready(T (&v)[R]) {
   else static_assert(R == 6 || R == 8, "dpp_ready: n + m of the bicycles");
 }
 
-template <class T, class Sys, bool WS = false, int G = kGroup> struct GroupWorker {
+// NH > 0: the horizon is the compile-time constant NH (the caller launches this form only with
+// c.N == NH): N, the layout offsets — GLayout(NH), the very constructor the host sizes the LDS
+// with — and every trip count that derives from them fold, and the two fast passes of the
+// sixteen-lane form run as straight-line code (backward_row_from<false>, forward_row).  NH == 0:
+// the horizon is c.N, read at run time.
+template <class T, class Sys, bool WS = false, int G = kGroup, int NH = 0> struct GroupWorker {
   static constexpr int n = Sys::n, m = Sys::m, W = n + m, NV = Sys::NVAR, NT = Sys::NTRIG;
   static constexpr int NA = n + 1;
   using Cfg = DevCfg<T, n, m>;
   using GL = GLayout<Sys, G>;
   static_assert(G == kGroup || G == 16, "eight lanes per problem, or one 16-lane DPP row");
   static_assert(G == kGroup || !WS, "the workspace form is built for eight lanes per problem");
+  static_assert(NH == 0 || (G == 16 && !WS), "the fixed-horizon form is the sixteen-lane LDS form");
+  static __host__ __device__ constexpr int horizon(int cfg_N) { return NH > 0 ? NH : cfg_N; }
   using GP = GroupPattern<Sys>;
   static_assert(GP::ok(), "plant does not have the column structure this kernel is written for");
   const Cfg& c;
@@ -201,7 +208,14 @@ template <class T, class Sys, bool WS = false, int G = kGroup> struct GroupWorke
   const Slice<T> S;  // this problem's LDS slice
   const T* const Qt; // the wavefront's copy of Q_terminal
   const int g;       // lane inside the group = column index
-  const int N;
+  const int N;       // (NH > 0: the constant NH)
+  // The bound of the loops that are to STAY loops in the fixed-horizon form — the entry rollout and
+  // the general passes, cold or once per launch: there the horizon as the run-time value it is in
+  // c.  With a constant bound the compiler unrolls all twenty steps of each (2.4 x the code).
+  __device__ __forceinline__ int loop_N() const {
+    if constexpr (NH > 0) return c.N;
+    else return N;
+  }
   int oR, oKk;       // where the records and the gains sit in the slice (the layout's by default;
                      // the speculative kernel gives each wavefront its own)
   T* T1c;            // this problem's exchange buffer
@@ -219,9 +233,9 @@ template <class T, class Sys, bool WS = false, int G = kGroup> struct GroupWorke
 #endif
 
   __device__ GroupWorker(const Cfg& c_, T* smem, int lane)
-      : GroupWorker(c_, smem + (lane / G) * GL(c_.N, WS).total,
-                    smem + GL(c_.N, WS).qt_base(), lane % G,
-                    GL(c_.N, WS).total) {
+      : GroupWorker(c_, smem + (lane / G) * GL(horizon(c_.N), WS).total,
+                    smem + GL(horizon(c_.N), WS).qt_base(), lane % G,
+                    GL(horizon(c_.N), WS).total) {
     const int p = lane / G;
     if constexpr (G == kGroup) T1c = smem + L.t1_base() + p * GL::kT1Stride;
     rho = (p >> 1) & 1;
@@ -256,8 +270,8 @@ template <class T, class Sys, bool WS = false, int G = kGroup> struct GroupWorke
 
   // slice: this problem's LDS slice of slice_words words; qt: Q_terminal in LDS
   __device__ GroupWorker(const Cfg& c_, T* slice, const T* qt, int g_, int slice_words)
-      : c(c_), L(c_.N, WS), S(make_slice(slice, slice_words, c_.trap, TAG_GROUP_LDS)), Qt(qt),
-        g(g_), N(c_.N) {
+      : c(c_), L(horizon(c_.N), WS), S(make_slice(slice, slice_words, c_.trap, TAG_GROUP_LDS)),
+        Qt(qt), g(g_), N(horizon(c_.N)) {
     oR = L.R; oKk = L.Kk;
     T1c = nullptr;  // set by the caller (with rho) before the first pass
     rho = 0;
@@ -335,6 +349,7 @@ template <class T, class Sys, bool WS = false, int G = kGroup> struct GroupWorke
     T x[n], u[m], xn[n], tr[NT];
 #pragma unroll
     for (int i = 0; i < n; i++) x[i] = S[XUo + i];
+    const int N = loop_N();
     for (int t = 0; t < N; t++) {
 #pragma unroll
       for (int a = 0; a < m; a++) u[a] = clip(S[XUo + t * W + n + a], -c.u_max[a], c.u_max[a]);
@@ -689,18 +704,46 @@ template <class T, class Sys, bool WS = false, int G = kGroup> struct GroupWorke
     for (int r = 0; r < n; r++) cdr[r] = (rsrc == r) ? cdt : T(0);
     struct Rec { T jv[NV], luu[m], c0, c1, l0, l1, lrow[m]; };
     Rec ra, rb;
+    // Fixed horizon, fast form: the pass is straight-line code, the step index a compile-time
+    // constant.  The per-lane words of record t are then read at (record 0 + the lane's offset),
+    // formed here once per pass, plus the immediate t RW — not at rec(t) + offset, a vector add per
+    // word and step.
+    constexpr bool FIXED = NH > 0 && !GENERAL;
+    const T* const R0 = rec(0);
+    const T *pc0 = R0, *pc1 = R0, *pl0 = R0, *pl1 = R0, *plu[m];
+#pragma unroll
+    for (int a = 0; a < m; a++) plu[a] = R0;
+    if constexpr (FIXED) {
+      pc0 = R0 + off_c0; pc1 = R0 + off_c1; pl0 = R0 + off_l0; pl1 = R0 + off_l1;
+#pragma unroll
+      for (int a = 0; a < m; a++) plu[a] = R0 + off_lu[a];
+    }
     auto load_record = [&](int t, Rec& r) __attribute__((always_inline)) {
-      const T* R = rec(t);
+      if constexpr (FIXED) {
+        const int o = t * GL::RW;
 #pragma unroll
-      for (int q = 0; q < NV; q++) r.jv[q] = R[GL::R_JV + q];
+        for (int q = 0; q < NV; q++) r.jv[q] = R0[o + GL::R_JV + q];
 #pragma unroll
-      for (int a = 0; a < m; a++) r.luu[a] = R[GL::R_LUU + a];
-      r.c0 = R[off_c0];
-      r.c1 = R[off_c1];
-      r.l0 = R[off_l0];
-      r.l1 = R[off_l1];
+        for (int a = 0; a < m; a++) r.luu[a] = R0[o + GL::R_LUU + a];
+        r.c0 = pc0[o];
+        r.c1 = pc1[o];
+        r.l0 = pl0[o];
+        r.l1 = pl1[o];
 #pragma unroll
-      for (int a = 0; a < m; a++) r.lrow[a] = R[off_lu[a]];
+        for (int a = 0; a < m; a++) r.lrow[a] = plu[a][o];
+      } else {
+        const T* R = rec(t);
+#pragma unroll
+        for (int q = 0; q < NV; q++) r.jv[q] = R[GL::R_JV + q];
+#pragma unroll
+        for (int a = 0; a < m; a++) r.luu[a] = R[GL::R_LUU + a];
+        r.c0 = R[off_c0];
+        r.c1 = R[off_c1];
+        r.l0 = R[off_l0];
+        r.l1 = R[off_l1];
+#pragma unroll
+        for (int a = 0; a < m; a++) r.lrow[a] = R[off_lu[a]];
+      }
     };
     // F[k][n + b] as a register operand
     auto f_entry = [&](auto k_, auto b_, const T (&jv)[NV]) __attribute__((always_inline)) {
@@ -814,20 +857,29 @@ template <class T, class Sys, bool WS = false, int G = kGroup> struct GroupWorke
       for (int i = 0; i < n; i++) va[i] = vn[i];
     };
     STAMP_BEGIN();  // (whole pass: per-phase stamps inside the step serialise what they measure)
-    int t = N - 1;
-    if constexpr (I2LQR_GROUP_UNROLL >= 4) {
-      for (; t >= 3; t -= 4) {
+    if constexpr (FIXED) {
+      // steps NH - 1 .. 0 in the same order, the two record sets in turn as below
+      static_for_i<0, NH>([&](auto i_) {
+        constexpr int i = decltype(i_)::value;
+        if constexpr (i % 2 == 0) step(NH - 1 - i, ra, rb);
+        else step(NH - 1 - i, rb, ra);
+      });
+    } else {
+      int t = loop_N() - 1;
+      if constexpr (I2LQR_GROUP_UNROLL >= 4) {
+        for (; t >= 3; t -= 4) {
+          step(t, ra, rb);
+          step(t - 1, rb, ra);
+          step(t - 2, ra, rb);
+          step(t - 3, rb, ra);
+        }
+      }
+      for (; t >= 1; t -= 2) {
         step(t, ra, rb);
         step(t - 1, rb, ra);
-        step(t - 2, ra, rb);
-        step(t - 3, rb, ra);
       }
+      if (t == 0) step(0, ra, rb);
     }
-    for (; t >= 1; t -= 2) {
-      step(t, ra, rb);
-      step(t - 1, rb, ra);
-    }
-    if (t == 0) step(0, ra, rb);
     STAMP_END(1);
     wave_sync();  // the forward pass reads the gain columns the other lanes stored
     return bad;
@@ -895,30 +947,41 @@ template <class T, class Sys, bool WS = false, int G = kGroup> struct GroupWorke
 #pragma unroll
       for (int i = 0; i < n; i++) x[i] = xn[i];
     };
-    int t = 0;
-    for (; t + 1 < N; t += 2) {
-      step(std::integral_constant<int, 0>{}, tr);  // x = x_{t+1}
-      T sc[NT], tr1[NT];
-      Sys::trig_heading_fast(half ? Sys::next_heading(c, x) : Sys::heading(x), sc, bad);
-#pragma unroll
-      for (int q = 0; q < NT; q++) pTR[NT + q] = sc[q];   // record t + 1 + half
-#pragma unroll
-      for (int q = 0; q < NT; q++) {
-        tr1[q] = bcast_mov<0>(sc[q]);
-        tr[q] = bcast_mov<8>(sc[q]);   // of x_{t+2}: the next pair's first step
-      }
-      step(std::integral_constant<int, 1>{}, tr1);  // x = x_{t+2}
-      pXo = pXo + 2 * W;
-      pXn = pXn + 2 * W;
-      pG = pG + 2 * (m * GL::KW);
-      pTR = pTR + 2 * NT;
+    // One pair of steps / the last step of an odd horizon.  (Macros, not lambdas: the run-time
+    // loop below compiles to exactly the code it had with its body written in place.)
+#define I2LQR_FORWARD_ROW_PAIR()                                                                   \
+    {                                                                                              \
+      step(std::integral_constant<int, 0>{}, tr); /* x = x_{t+1} */                                \
+      T sc[NT], tr1[NT];                                                                           \
+      Sys::trig_heading_fast(half ? Sys::next_heading(c, x) : Sys::heading(x), sc, bad);           \
+      _Pragma("unroll") for (int q = 0; q < NT; q++) pTR[NT + q] = sc[q]; /* record t + 1 + half */ \
+      _Pragma("unroll") for (int q = 0; q < NT; q++) {                                             \
+        tr1[q] = bcast_mov<0>(sc[q]);                                                              \
+        tr[q] = bcast_mov<8>(sc[q]); /* of x_{t+2}: the next pair's first step */                  \
+      }                                                                                            \
+      step(std::integral_constant<int, 1>{}, tr1); /* x = x_{t+2} */                               \
+      pXo = pXo + 2 * W;                                                                           \
+      pXn = pXn + 2 * W;                                                                           \
+      pG = pG + 2 * (m * GL::KW);                                                                  \
+      pTR = pTR + 2 * NT;                                                                          \
     }
-    if (t < N) {  // odd horizon: the last step, and the sin / cos of x_N for the records
-      step(std::integral_constant<int, 0>{}, tr);
-      Sys::template trig_g<false>(x, tr, bad);
-#pragma unroll
-      for (int q = 0; q < NT; q++) S[TRn + N * NT + q] = tr[q];
+#define I2LQR_FORWARD_ROW_LAST() /* and the sin / cos of x_N for the records */                    \
+    {                                                                                              \
+      step(std::integral_constant<int, 0>{}, tr);                                                  \
+      Sys::template trig_g<false>(x, tr, bad);                                                     \
+      _Pragma("unroll") for (int q = 0; q < NT; q++) S[TRn + N * NT + q] = tr[q];                  \
     }
+    if constexpr (NH > 0) {
+      // fixed horizon: the pairs in a row, the bumps of the bases fold into immediate offsets
+      static_for_i<0, NH / 2>([&](auto) __attribute__((always_inline)) I2LQR_FORWARD_ROW_PAIR());
+      if constexpr (NH % 2 != 0) I2LQR_FORWARD_ROW_LAST()
+    } else {
+      int t = 0;
+      for (; t + 1 < N; t += 2) I2LQR_FORWARD_ROW_PAIR()
+      if (t < N) I2LQR_FORWARD_ROW_LAST()
+    }
+#undef I2LQR_FORWARD_ROW_PAIR
+#undef I2LQR_FORWARD_ROW_LAST
     const T cost = terminal_cost(x, xT);
     wave_sync();
     return cost;
@@ -932,6 +995,7 @@ template <class T, class Sys, bool WS = false, int G = kGroup> struct GroupWorke
                                        bool* bad) const {
     if constexpr (G == 16 && !GENERAL && Sys::kHeadingAhead && m == 2)
       return forward_row(XUo, XUn, TRn, xT, bad);
+    const int N = loop_N();
     T x[n], u[m], xn[n], tr[NT];
 #pragma unroll
     for (int i = 0; i < n; i++) x[i] = S[XUo + i];
@@ -1036,9 +1100,11 @@ __device__ __forceinline__ int idx_div(int e, int d, float rcp_d) {
 // WS: records and gains in the HBM workspace `ws` (GLayout::ws_words() words per problem, sized for
 // whole wavefronts: ceil(B / 8) * 8 problems), four wavefronts per CU instead of two — the form
 // for more than 4096 problems on the problem-major layout.  Same arithmetic, bit-identical.
-template <class T, class Sys, int H = 1, bool WS = false, int G = kGroup>
-__global__ __launch_bounds__(64 * H) void k_group_iterate(const DevCfg<T, Sys::n, Sys::m> c,
-                                                          const IterArgs<T> a, T* ws = nullptr) {
+// The body is shared by two kernel symbols: k_group_iterate (NH = 0: the horizon is c.N) and
+// k_group_iterate_fixed (NH > 0: the horizon is the compile-time constant NH == c.N).
+template <class T, class Sys, int H, bool WS, int G, int NH>
+__device__ __forceinline__ void group_iterate_body(const DevCfg<T, Sys::n, Sys::m>& c,
+                                                   const IterArgs<T>& a, T* ws) {
   static_assert(!(WS && H > 1), "the workspace form runs without helper wavefronts");
   constexpr int n = Sys::n, m = Sys::m, W = n + m;
   // overlapped schedule (sixteen lanes, H >= 3): the helpers compute all the records while the
@@ -1061,8 +1127,8 @@ __global__ __launch_bounds__(64 * H) void k_group_iterate(const DevCfg<T, Sys::n
   // that every lane of the wavefront runs the same control flow
   const bool real = prob0 < a.B;
   const int64_t prob = real ? prob0 : a.B - 1;
-  GroupWorker<T, Sys, WS, G> w(c, smem, lane);
-  const int N = c.N, g = w.g;
+  GroupWorker<T, Sys, WS, G, NH> w(c, smem, lane);
+  const int N = NH > 0 ? NH : c.N, g = w.g;
   const float rN = 1.0f / (float)N, rN1 = 1.0f / (float)(N + 1), rnN = 1.0f / (float)(n * N);
   const GL& L = w.L;
   const auto S = w.S;
@@ -1316,6 +1382,27 @@ __global__ __launch_bounds__(64 * H) void k_group_iterate(const DevCfg<T, Sys::n
     }
     if (a.pick_part) pick_epilogue(a, cand, prob, ci);
   }
+}
+
+template <class T, class Sys, int H = 1, bool WS = false, int G = kGroup>
+__global__ __launch_bounds__(64 * H) void k_group_iterate(const DevCfg<T, Sys::n, Sys::m> c,
+                                                          const IterArgs<T> a, T* ws = nullptr) {
+  group_iterate_body<T, Sys, H, WS, G, 0>(c, a, ws);
+}
+
+// Fixed-horizon form of the sixteen-lane LDS kernel (G = 16, WS = false): the same body with the
+// horizon NH a compile-time constant — in real use a constant of the handle (i2lqr_config.N).  N is
+// no operand any more: the fast backward pass is NH steps and the fast forward pass NH / 2 pairs of
+// straight-line code, every record, gain and trajectory access a base register plus an immediate,
+// no back-edge and no per-step address arithmetic; the general forms and the entry rollout stay
+// loops.  Same operations in the same order: bit-identical to k_group_iterate<T, Sys, H, false, 16>
+// at N = NH.  Launched by group16_iterate for the horizons of I2LQR_GROUP_FIXED_HORIZONS
+// (i2lqr_group.h); instantiated in i2lqr_group_fixed.hip.
+template <class T, class Sys, int H, int NH>
+__global__ __launch_bounds__(64 * H) void k_group_iterate_fixed(const DevCfg<T, Sys::n, Sys::m> c,
+                                                                const IterArgs<T> a) {
+  static_assert(NH > 0, "a compile-time horizon");
+  group_iterate_body<T, Sys, H, false, 16, NH>(c, a, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------

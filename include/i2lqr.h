@@ -306,6 +306,14 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     per-step records while the main wavefront computes the terminal value block
  *                     (kept over rejected iterations), and the helpers store the gains at exit.
  *                     Same arithmetic, bit-identical.
+ *   "group_fixed_horizon"  sixteen-lane kernel, horizons the fixed-horizon form is built for
+ *                     (N = 20: csrc/i2lqr_group.h, I2LQR_GROUP_FIXED_HORIZONS): 1 / automatic:
+ *                     k_group_iterate_fixed — the horizon is a compile-time constant of the kernel
+ *                     instead of an operand read from the configuration, its two fast passes are
+ *                     straight-line code without loop branches or per-step address arithmetic;
+ *                     0 forces k_group_iterate.  Same operations in the same order, bit-identical;
+ *                     same batch thresholds and helper wavefronts.  For any other horizon the
+ *                     option has no effect (and is no error).
  *   "speculate"       ("group_lanes" 8 / automatic) 1: the speculative form of the eight-lane
  *                     kernel — V wavefronts per eight problems (three up to 512 problems, two
  *                     above and in the tail of the chunked solves), wavefront v runs the iteration
