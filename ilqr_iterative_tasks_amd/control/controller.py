@@ -85,6 +85,9 @@ class iLqr(ControlBase):
         # device_rounds: run the three outer rounds (select / solve / relaxed cost / pick) on the
         # GPU with one read-back per control step (control/device_round.py; independent lamb)
         assert not device_rounds or lamb_mode == "independent"
+        if getattr(solver, "line_search", 1) > 1 and (lamb_mode == "chained" or device_rounds):
+            raise ValueError("a solver with line_search > 1 is for lamb_mode=\"independent\" without "
+                             "device_rounds: the chain kernel and the device rounds have no line search")
         self.ilqr_param = ilqr_param
         self.system_param = system_param
         self.obstacle = obstacle          # public: scenario scripts swap it between laps

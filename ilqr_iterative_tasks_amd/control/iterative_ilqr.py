@@ -17,11 +17,19 @@ from .params import config_from_params, obstacle_record
 class HipCandidateSolver:
     """Batched ilqr() on the GPU: host NumPy in, host NumPy out, device work through BatchedILQR.
 
-    One BatchedILQR (one C-ABI handle) is cached per distinct configuration."""
+    One BatchedILQR (one C-ABI handle) is cached per distinct configuration.
 
-    def __init__(self, device="cuda:0", dtype="f64"):
+    line_search = 2, 4 or 8: every handle is created problem-major, whatever layout the library
+    recommends for the batch, with the "line_search" option set (include/i2lqr.h: that many step
+    sizes 2^-j per iteration on k_iterate_ls — not the reference's algorithm); independent lamb
+    only, solve_chained raises."""
+
+    def __init__(self, device="cuda:0", dtype="f64", line_search=1):
+        if int(line_search) not in (-1, 0, 1, 2, 4, 8):
+            raise ValueError(f"line_search is 2, 4 or 8 step sizes, or -1 / 0 / 1 (off): got {line_search}")
         self.device = device
         self.dtype = dtype
+        self.line_search = int(line_search) if int(line_search) > 1 else 1
         self._solvers = {}
 
     def _solver(self, cfg, B=None, early_exit=True):
@@ -29,7 +37,11 @@ class HipCandidateSolver:
         for batches of that size (i2lqr_recommended_layout): a caller who hands 65536 candidates
         to solve() gets the one-problem-per-lane kernels without knowing that they exist."""
         from ..solver import BatchedILQR
-        if B is not None:
+        if self.line_search > 1:  # k_iterate_ls is a problem-major kernel
+            if cfg.layout != 0:
+                cfg = cfg.copy()
+                cfg.layout = 0
+        elif B is not None:
             lay = BatchedILQR.recommended_layout(cfg, B, early_exit)
             if lay != cfg.layout:
                 cfg = cfg.copy()
@@ -37,6 +49,8 @@ class HipCandidateSolver:
         key = bytes(C.string_at(C.byref(cfg), C.sizeof(cfg)))
         if key not in self._solvers:
             self._solvers[key] = BatchedILQR(cfg, self.device)
+            if self.line_search > 1:
+                self._solvers[key].set_option("line_search", self.line_search)
         return self._solvers[key]
 
     def _round_buffers(self, cfg, x0, x_terms, qfun, lamb0, obs_rec, early_exit):
@@ -334,6 +348,9 @@ class HipCandidateSolver:
         the same inputs: bit-identical to the step-by-step form.
         Returns one dict(U, X, lamb, cost, iters, status) per chain (host arrays, leading axis k_a)."""
         import torch
+        if self.line_search > 1:
+            raise ValueError("solve_chained: line_search is built for independent lamb (the chain "
+                             "kernel has no line search)")
         chains = [np.atleast_2d(np.asarray(xt, float)) for xt in x_terms_by_chain]
         widths = [len(c) for c in chains]
         width = max(widths)

@@ -22,6 +22,7 @@
 #include "i2lqr_lane.hpp"
 #include "i2lqr_select.hpp"
 #include "i2lqr_wave.hpp"
+#include "i2lqr_wave_ls.h"
 
 #include "i2lqr_lane12.h"
 
@@ -291,6 +292,7 @@ struct i2lqr_handle {
   int opt_spec;   // eight-lane kernel: speculative form (2-3 wavefronts per eight problems); -1 = automatic
   int opt_group_ws;  // eight-lane kernel: workspace form (records / gains in HBM); -1 = automatic
   int opt_group_overlap;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; -1 = automatic (on)
+  int opt_ls;  // one-problem-per-wavefront kernel: step sizes of the parallel line search (k_iterate_ls): 2, 4, 8; 0: off
   int opt_group_fixed;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; -1 = automatic (on)
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
   // it into its kernel, otherwise the call runs the separate kernels.  The pointer to the call's
@@ -327,7 +329,7 @@ namespace {
 
 // Which fused kernel a problem-major call runs on: ONE function, used by the launchers and by
 // i2lqr_iterate_kernel / i2lqr_solve_kernel (what bench.py labels its results with).
-enum FusedKernel { K_WAVE, K_GROUP, K_GROUP16, K_GROUP_WS, K_SPEC, K_SPEC16, K_QUAD, K_INVALID };
+enum FusedKernel { K_WAVE, K_WAVE_LS, K_GROUP, K_GROUP16, K_GROUP_WS, K_SPEC, K_SPEC16, K_QUAD, K_INVALID };
 // (measured on the 256-CU chip; DeviceGeometry::scaled() elsewhere)
 constexpr int64_t kAutoGroupBatch = 1024;  // eight-lane kernel from here (automatic)
 constexpr int64_t kAutoSpecBatch = 12288;  // speculative form for solves up to here (automatic)
@@ -336,6 +338,16 @@ constexpr int64_t kAutoSpecBatch = 12288;  // speculative form for solves up to 
 FusedKernel select_fused(const i2lqr_handle* h, int64_t B, bool early_exit, const char** why) {
   static const char* none = "";
   if (!why) why = &none;
+  // "line_search": every call runs on the line-search form of the one-problem-per-wavefront kernel
+  // (k_iterate_ls, i2lqr_wave_ls.hip), whatever the batch size
+  if (h->opt_ls > 1) {
+    if (h->opt_group == 8 || h->opt_group == 16) {
+      *why = "\"line_search\" runs on the one-problem-per-wavefront kernel: not together with "
+             "\"group_lanes\" = 8 or 16";
+      return K_INVALID;
+    }
+    return K_WAVE_LS;
+  }
   const bool m2 = h->cfg.m == 2 && h->cfg.n + h->cfg.m <= 8;
   const bool q16 = h->cfg.n + h->cfg.m == 16;
   if (m2) {
@@ -543,6 +555,9 @@ template <class T, class Sys> struct Launch {
           return I2LQR_OK;
         }
         break;
+      case K_WAVE_LS:
+        HIP_TRY(wave_ls_iterate<T>(h->cfg, a, h->opt_ls, h->lds_bytes, s));
+        return I2LQR_OK;
       case K_WAVE:
         break;
     }
@@ -1539,6 +1554,7 @@ int i2lqr_create(const i2lqr_config* cfg, i2lqr_handle** out) {
   h->opt_merge = h->opt_ckpt = h->opt_spec = h->opt_stagger = h->opt_group_ws = -1;
   h->opt_group_overlap = -1;
   h->opt_group_fixed = -1;
+  h->opt_ls = 0;
   h->wave_tail = -1;
   h->opt_first_chunk = -1;
   h->opt_fuse = -1;
@@ -1789,6 +1805,14 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
                 "only (make -C ilqr_iterative_tasks_amd/csrc debug)");
 #endif
   }
+  else if (!strcmp(name, "line_search")) {
+    if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4 && v != 8)
+      return fail(I2LQR_ERR_INVALID, "\"line_search\" is 2, 4 or 8 step sizes, or -1 / 0 / 1 (off)");
+    if (v > 1 && h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR)
+      return fail(I2LQR_ERR_UNSUPPORTED, "\"line_search\" is built for the problem-major layout (the "
+                  "one-problem-per-wavefront kernel)");
+    h->opt_ls = v > 1 ? v : 0;
+  }
   else if (!strcmp(name, "group_lanes")) {
     if (v != -1 && v != 8 && v != 16 && v != 64)
       return fail(I2LQR_ERR_INVALID, "\"group_lanes\" is 8, 16, 64 or -1");
@@ -1816,6 +1840,7 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
     case K_GROUP16: return "k_group_iterate (sixteen lanes)";
     case K_GROUP_WS: return "k_group_iterate (workspace form)";
     case K_QUAD: return "k_quad_iterate";
+    case K_WAVE_LS: return "k_iterate (line search)";
     case K_WAVE: return "k_iterate";
     default: return "unsupported";  // the launch returns I2LQR_ERR_UNSUPPORTED
   }
@@ -1904,6 +1929,10 @@ int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void
   if (!X || !U || !x_term || !lamb || !cost) return fail(I2LQR_ERR_INVALID, "null buffer");
   if ((K == nullptr) != (k == nullptr))
     return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
+  if (h->opt_ls > 1)
+    return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which has "
+                "no line search: switch \"line_search\" off, or solve the chain steps one after the "
+                "other");
   const int rc = dispatch(h, [&](auto L) {
     return L.solve_chained(h, chains, chain_len, X, U, x_term, lamb, obs, cost, K, k, iters, status,
                            (hipStream_t)stream);

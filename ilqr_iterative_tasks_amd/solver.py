@@ -150,8 +150,9 @@ class BatchedILQR:
     def set_option(self, name: str, value: int) -> None:
         """Scheduling options (i2lqr_set_option in include/i2lqr.h); -1 restores the automatic
         choice.  Lane layouts: "defer_states", "reroll_nominal", "lds_gain_steps", "wave_tail";
-        problem-major layout: "group_lanes" (8 / 16 / 64), "speculate", "per_step_jacobians".  All
-        but "wave_tail" and "group_lanes" leave the results bit-identical."""
+        problem-major layout: "group_lanes" (8 / 16 / 64), "speculate", "per_step_jacobians",
+        "line_search" (2 / 4 / 8 step sizes per iteration on k_iterate_ls; 0 off).  All but
+        "wave_tail", "group_lanes" and "line_search" leave the results bit-identical."""
         self._check(self.lib.i2lqr_set_option(self._handle, name.encode(), int(value)))
 
     def iterate_kernel(self, B: int) -> str:

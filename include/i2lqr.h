@@ -336,6 +336,24 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     Riccati recursion has no Jacobian refresh; doubles the LDS per problem.
  *                     Automatic: on while every wavefront of the launch fits on the chip at once
  *                     (n <= 6 systems).
+ *   "line_search"     2, 4 or 8: every iteration of i2lqr_iterate / i2lqr_solve tries that many step
+ *                     sizes alpha_j = 2^-j (j = 0 ... value - 1) instead of the reference's one full
+ *                     step — NOT the reference's algorithm (control/iterative_ilqr.py:74-84 leaves a
+ *                     rejected step to the lamb schedule alone).  After the backward pass (unchanged)
+ *                     candidate j rolls out u'_t = clip((u_t + alpha_j k_t) + K_t (x'_t - x_t)) with
+ *                     the forward pass's cost (:151); j* = argmin_j cost_j (a NaN cost never wins,
+ *                     ties go to the smallest j, j* = 0 if no candidate has a cost below +inf); the
+ *                     reference's accept / reject then runs unchanged with cost_new = cost_j*.  The
+ *                     gains K, k a call returns are the backward pass's, NOT scaled by alpha_j*.
+ *                     While it is on EVERY call of the handle, whatever the batch size, runs on
+ *                     k_iterate_ls — one problem per wavefront, lane l rolls out candidate l mod
+ *                     value, so the candidates share the one serial rollout k_iterate runs on all 64
+ *                     lanes (three plants, both precisions, with or without stage weights);
+ *                     i2lqr_iterate_pick takes its unfused form; i2lqr_solve_chained and a forced
+ *                     "group_lanes" 8 or 16 answer I2LQR_ERR_UNSUPPORTED.  -1, 0 or 1: off (the
+ *                     default: the iteration above with one step is the reference's).  Any other
+ *                     value is I2LQR_ERR_INVALID; a batch-minor / batch-tiled handle answers
+ *                     I2LQR_ERR_UNSUPPORTED to 2, 4 or 8.
  *   "stagger"         lane layouts (k_lane_iterate_rows, k_lane_iterate): every second half-thousand
  *                     of workgroups starts value x ~8000 cycles late, so that half of the
  *                     wavefronts stream their gains (forward pass) while the other half computes
@@ -352,7 +370,7 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
 int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value);
 
 /* Name of the kernel i2lqr_iterate (fixed iteration count) launches for a batch of B problems
- * with the handle's current options: "k_iterate", "k_group_iterate", "k_group_iterate (sixteen
+ * with the handle's current options: "k_iterate", "k_iterate (line search)", "k_group_iterate", "k_group_iterate (sixteen
  * lanes)", "k_group_iterate (workspace form)", "k_group_spec", "k_group_spec (sixteen lanes)",
  * "k_quad_iterate", "k_lane_iterate", "k_lane_iterate_pair" (the helper-wavefront form),
  * "k_lane_iterate_rows"; "unsupported" if a forced option cannot be honoured and the launch would

@@ -46,7 +46,8 @@ OPTIONS = {"defer_states": (0, 1), "reroll_nominal": (0, 1), "lds_gain_steps": (
            "per_step_jacobians": (0, 1), "wave_tail": (0, 512, 2048, 12288, 65536),
            "first_chunk": (1, 4, 8, 12, 150), "helper_wavefront": (0, 1), "state_buffers": (0, 1),
            "chunk_step": (1, 2, 4, 9), "speculate": (0, 1), "group_workspace": (0, 1),
-           "group_lanes": (8, 16, 64), "fused_compaction": (0, 1), "final_round": (0, 1, 2, 3, 5)}
+           "group_lanes": (8, 16, 64), "fused_compaction": (0, 1), "final_round": (0, 1, 2, 3, 5),
+           "line_search": (0, 2, 4, 8)}
 
 
 class Arena:
