@@ -2,8 +2,6 @@
 // kernel dispatch.  No exception crosses the boundary; every entry point returns an int code and
 // records a thread-local message for i2lqr_last_error().
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <rccl/rccl.h>  // types and prototypes only: the library is bound at run time (rccl_api())
 
 #include <atomic>
 #include <cmath>
@@ -19,12 +17,12 @@
 #include "i2lqr_devcfg.hpp"
 #include "i2lqr_geometry.hpp"
 #include "i2lqr_group.h"
-#include "i2lqr_lane.hpp"
-#include "i2lqr_select.hpp"
-#include "i2lqr_wave.hpp"
-#include "i2lqr_wave_ls.h"
-
+#include "i2lqr_host.hpp"
+#include "i2lqr_kernels.h"
 #include "i2lqr_lane12.h"
+#include "i2lqr_rccl.hpp"
+#include "i2lqr_select.hpp"
+#include "i2lqr_wave_ls.h"
 
 #define I2LQR_DRY_RUN_LANE 1
 #include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
@@ -32,138 +30,16 @@
 using namespace i2lqr;
 
 namespace {
-
 thread_local char g_err[512] = "";
+}
 
-int fail(int code, const char* fmt, ...) {
+int i2lqr::fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      return fail(I2LQR_ERR_LAUNCH, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-  } while (0)
-
-}  // namespace
-
-#ifdef I2LQR_DRY_RUN
-#include <cxxabi.h>
-
-#include <string>
-#include <vector>
-namespace i2lqr {
-namespace dry {
-namespace {
-struct State {
-  std::mutex mu;
-  std::vector<std::pair<uintptr_t, uintptr_t>> ranges;
-  std::string text;
-  int64_t launches = 0, violations = 0;
-};
-State& st() {
-  static State s;
-  return s;
-}
-}  // namespace
-bool on() {
-  static const bool v = [] {
-    const char* e = getenv("I2LQR_DRY_RUN");
-    return e && e[0] == '1';
-  }();
-  return v;
-}
-void allow(const void* base, size_t bytes) {
-  std::lock_guard<std::mutex> lock(st().mu);
-  st().ranges.emplace_back((uintptr_t)base, (uintptr_t)base + bytes);
-}
-void reset() {
-  std::lock_guard<std::mutex> lock(st().mu);
-  st().ranges.clear();
-  st().text.clear();
-  st().launches = st().violations = 0;
-}
-// the record being built by this thread (launch(): record, the arguments, end)
-thread_local std::string t_line, t_kernel;
-void record(const char* expr, const void* kernel, dim3 grid, dim3 block, size_t lds) {
-  t_kernel = expr;
-  Dl_info info;
-  if (dladdr(kernel, &info) && info.dli_sname && info.dli_saddr == kernel) {
-    int status = 0;
-    char* name = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &status);
-    t_kernel = status == 0 && name ? name : info.dli_sname;
-    free(name);
-  }
-  char line[96];
-  snprintf(line, sizeof(line), " grid %u block %u lds %zu", grid.x, block.x, lds);
-  t_line = "launch " + t_kernel + line;
-  std::lock_guard<std::mutex> lock(st().mu);
-  st().launches++;
-  const DeviceGeometry& g = device_geometry();
-  if (grid.x == 0 || block.x == 0 || block.x > 1024 || lds > g.max_dyn_lds) {
-    st().violations++;
-    st().text += "VIOLATION " + t_kernel + ": launch shape" + line + "\n";
-  }
-}
-void ptr(const char* field, const void* p) {
-  char buf[96];
-  if (!p) {
-    snprintf(buf, sizeof(buf), " %s=0", field);
-    t_line += buf;
-    return;
-  }
-  std::lock_guard<std::mutex> lock(st().mu);
-  const uintptr_t a = (uintptr_t)p;
-  for (size_t r = 0; r < st().ranges.size(); r++)
-    if (a >= st().ranges[r].first && a < st().ranges[r].second) {
-      snprintf(buf, sizeof(buf), " %s=r%zu+%zu", field, r, (size_t)(a - st().ranges[r].first));
-      t_line += buf;
-      return;
-    }
-  snprintf(buf, sizeof(buf), " %s=?", field);
-  t_line += buf;
-  st().violations++;
-  char line[160];
-  snprintf(line, sizeof(line), ": %s = %p lies in no declared range\n", field, p);
-  st().text += "VIOLATION " + t_kernel + line;
-}
-void val(const char* field, int64_t v) {
-  char buf[96];
-  snprintf(buf, sizeof(buf), " %s=%lld", field, (long long)v);
-  t_line += buf;
-}
-void end() {
-  std::lock_guard<std::mutex> lock(st().mu);
-  if (st().text.size() < (1u << 21)) st().text += t_line + "\n";
-}
-int64_t report(char* buf, int64_t n) {
-  std::lock_guard<std::mutex> lock(st().mu);
-  if (buf && n > 0) {
-    // violations first: the buffer may be shorter than the launch log
-    std::string out;
-    size_t pos = 0;
-    while ((pos = st().text.find("VIOLATION", pos)) != std::string::npos) {
-      const size_t end = st().text.find('\n', pos);
-      out += st().text.substr(pos, end == std::string::npos ? std::string::npos : end - pos + 1);
-      if (end == std::string::npos) break;
-      pos = end + 1;
-    }
-    out += st().text;
-    snprintf(buf, (size_t)n, "%s", out.c_str());
-  }
-  st().text.clear();
-  const int64_t v = st().violations;
-  st().violations = 0;
-  return v;
-}
-}  // namespace dry
-}  // namespace i2lqr
-#endif
 
 namespace i2lqr {
 // hipDeviceGetAttribute once per device; I2LQR_FAKE_CUS=<n> (a debug override, parity tests of the
@@ -275,25 +151,25 @@ struct i2lqr_handle {
   int lanes;        // lanes of a wavefront that cooperate on one problem (1: batch-minor layout)
   size_t lds_bytes; // dynamic LDS per workgroup (one wavefront)
   int device;
-  void* ws;         // caller-owned scratch of the batch-minor kernels
-  int64_t ws_bytes;
-  int64_t compact_min_batch;  // i2lqr_solve uses the chunked, compacting form from this batch; 0: never; -1: automatic
+  void* ws = nullptr;  // caller-owned scratch of the batch-minor kernels
+  int64_t ws_bytes = 0;
+  int64_t compact_min_batch = -1;  // i2lqr_solve uses the chunked, compacting form from this batch; 0: never; -1: automatic
   // scheduling options of the one-problem-per-lane kernels (i2lqr_set_option); -1 = automatic
-  int opt_defer, opt_reroll, opt_lds_steps, opt_merge, opt_ckpt, opt_stagger;
-  int wave_tail;  // chunked solve: finish <= this many survivors with one problem per wavefront (0: off, -1: automatic)
-  int opt_pair;  // bicycles' lane kernel (fp64 and fp32, with or without stage weights): workgroups of two wavefronts (main + helper); -1 = automatic
-  int opt_two_x;  // ... its second state buffer (no re-roll of accepted steps); -1 = automatic
-  int opt_chunk_step;  // chunked solve: length of the chunk that follows the first (automatic: 4); a schedule to measure against
-  int opt_fuse;  // chunked solve: compaction folded into the chunk kernels' exit (round 6); 0: k_lane_compact launches; -1 = automatic (on)
-  int opt_final_round;  // chunked solve: the round whose tail kernel takes every survivor and ends the schedule; 0: never; -1 = automatic
-  int opt_first_chunk;  // chunked solve: pinned length of the first chunk, no extension chunks (a hand-tuned schedule to measure the data-driven one against); -1 = automatic
-  int opt_fstep;  // one-problem-per-wavefront kernel: per-step Jacobian matrices in LDS; -1 = automatic
-  int opt_group;  // problem-major layout: lanes per problem of the fused kernels: 8, 64; -1 = automatic
-  int opt_spec;   // eight-lane kernel: speculative form (2-3 wavefronts per eight problems); -1 = automatic
-  int opt_group_ws;  // eight-lane kernel: workspace form (records / gains in HBM); -1 = automatic
-  int opt_group_overlap;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; -1 = automatic (on)
-  int opt_ls;  // one-problem-per-wavefront kernel: step sizes of the parallel line search (k_iterate_ls): 2, 4, 8; 0: off
-  int opt_group_fixed;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; -1 = automatic (on)
+  int opt_defer = -1, opt_reroll = -1, opt_lds_steps = -1, opt_merge = -1, opt_ckpt = -1, opt_stagger = -1;
+  int wave_tail = -1;  // chunked solve: finish <= this many survivors with one problem per wavefront (0: off, -1: automatic)
+  int opt_pair = -1;  // bicycles' lane kernel (fp64 and fp32, with or without stage weights): workgroups of two wavefronts (main + helper); -1 = automatic
+  int opt_two_x = -1;  // ... its second state buffer (no re-roll of accepted steps); -1 = automatic
+  int opt_chunk_step = -1;  // chunked solve: length of the chunk that follows the first (automatic: 4); a schedule to measure against
+  int opt_fuse = -1;  // chunked solve: compaction folded into the chunk kernels' exit (round 6); 0: k_lane_compact launches; -1 = automatic (on)
+  int opt_final_round = -1;  // chunked solve: the round whose tail kernel takes every survivor and ends the schedule; 0: never; -1 = automatic
+  int opt_first_chunk = -1;  // chunked solve: pinned length of the first chunk, no extension chunks (a hand-tuned schedule to measure the data-driven one against); -1 = automatic
+  int opt_fstep = -1;  // one-problem-per-wavefront kernel: per-step Jacobian matrices in LDS; -1 = automatic
+  int opt_group = -1;  // problem-major layout: lanes per problem of the fused kernels: 8, 64; -1 = automatic
+  int opt_spec = -1;   // eight-lane kernel: speculative form (2-3 wavefronts per eight problems); -1 = automatic
+  int opt_group_ws = -1;  // eight-lane kernel: workspace form (records / gains in HBM); -1 = automatic
+  int opt_group_overlap = -1;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; -1 = automatic (on)
+  int opt_ls = 0;  // one-problem-per-wavefront kernel: step sizes of the parallel line search (k_iterate_ls): 2, 4, 8; 0: off
+  int opt_group_fixed = -1;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; -1 = automatic (on)
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
   // it into its kernel, otherwise the call runs the separate kernels.  The pointer to the call's
   // epilogue is THREAD-LOCAL (t_epi below), not handle state: two host threads inside
@@ -312,12 +188,12 @@ struct i2lqr_handle {
   // are in flight at the same time (two streams) draw from different words as long as fewer than
   // kTickets of them overlap; their part[] workspaces are the caller's and must differ.
   static constexpr unsigned kTickets = 16;
-  unsigned* ticket;
-  std::atomic<unsigned> ticket_next;
+  unsigned* ticket = nullptr;
+  std::atomic<unsigned> ticket_next{0};
   // i2lqr_sharded_round_flat: the event that orders the side stream behind the shard's solve and
   // the one a later round waits for before it reuses the buffers (created on first use)
-  hipEvent_t ev_ready, ev_side_done;
-  bool side_pending;  // ev_side_done has been recorded at least once
+  hipEvent_t ev_ready = nullptr, ev_side_done = nullptr;
+  bool side_pending = false;  // ev_side_done has been recorded at least once
   DeviceGeometry geo;  // of h->device, queried in i2lqr_create (i2lqr_geometry.hpp)
 };
 
@@ -1203,6 +1079,20 @@ std::unordered_set<const i2lqr_handle*>& live_handles() {
   return set;
 }
 
+// What the one-problem-per-lane kernels need of the weights (they store only the upper triangles
+// of the value function): nullptr, or what is not symmetric
+const char* lane_asymmetry(const i2lqr_config& cfg) {
+  for (int i = 0; i < cfg.n; i++)
+    for (int j = 0; j < i; j++)
+      if (cfg.Q[i * I2LQR_MAX_N + j] != cfg.Q[j * I2LQR_MAX_N + i] ||
+          cfg.Qt[i * I2LQR_MAX_N + j] != cfg.Qt[j * I2LQR_MAX_N + i])
+        return "symmetric Q and Qterminal";
+  for (int a = 0; a < cfg.m; a++)
+    for (int b = 0; b < a; b++)
+      if (cfg.R[a * I2LQR_MAX_M + b] != cfg.R[b * I2LQR_MAX_M + a]) return "a symmetric R";
+  return nullptr;
+}
+
 int check_common(const i2lqr_handle* h, int64_t B) {
   if (!h) return fail(I2LQR_ERR_INVALID, "null handle");
   if (B < 0) return fail(I2LQR_ERR_INVALID, "negative batch %lld", (long long)B);
@@ -1213,18 +1103,11 @@ int check_common(const i2lqr_handle* h, int64_t B) {
 // ---- arg-min kernels (flat, first index wins ties) -------------------------------------------
 // FINAL: a single workgroup scans the whole vector and writes the result itself (small batches:
 // one launch instead of two)
-template <class T, bool FINAL = false>
-__global__ __launch_bounds__(256) void k_argmin_partial(int64_t B, const T* cost, MinPair<T>* part,
-                                                        int64_t* best_idx = nullptr,
-                                                        T* best_cost = nullptr) {
+// The 256-thread reduction of the kernels below: every thread brings the best (value, index) of its
+// own scan (index -1: none), all of them return the workgroup's (index -1: empty).
+template <class T> __device__ MinPair<T> block_argmin(T bv, int64_t bi) {
   __shared__ T sv[256];
   __shared__ int64_t si[256];
-  T bv = T(0);
-  int64_t bi = -1;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < B; i += (int64_t)gridDim.x * 256) {
-    const T v = cost[i];
-    if (better(v, i, bv, bi)) { bv = v; bi = i; }
-  }
   sv[threadIdx.x] = bv;
   si[threadIdx.x] = bi;
   __syncthreads();
@@ -1239,13 +1122,27 @@ __global__ __launch_bounds__(256) void k_argmin_partial(int64_t B, const T* cost
     }
     __syncthreads();
   }
+  return MinPair<T>{sv[0], si[0]};
+}
+
+template <class T, bool FINAL = false>
+__global__ __launch_bounds__(256) void k_argmin_partial(int64_t B, const T* cost, MinPair<T>* part,
+                                                        int64_t* best_idx = nullptr,
+                                                        T* best_cost = nullptr) {
+  T bv = T(0);
+  int64_t bi = -1;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < B; i += (int64_t)gridDim.x * 256) {
+    const T v = cost[i];
+    if (better(v, i, bv, bi)) { bv = v; bi = i; }
+  }
+  const MinPair<T> r = block_argmin(bv, bi);
   if (threadIdx.x == 0) {
     if constexpr (FINAL) {
-      *best_idx = si[0];
-      *best_cost = si[0] >= 0 ? sv[0] : (T)INFINITY;
+      *best_idx = r.i;
+      *best_cost = r.i >= 0 ? r.v : (T)INFINITY;
     } else {
-      part[blockIdx.x].v = sv[0];
-      part[blockIdx.x].i = si[0];
+      part[blockIdx.x].v = r.v;
+      part[blockIdx.x].i = r.i;
     }
   }
 }
@@ -1253,8 +1150,6 @@ __global__ __launch_bounds__(256) void k_argmin_partial(int64_t B, const T* cost
 template <class T>
 __global__ __launch_bounds__(256) void k_argmin_final(int nparts, const MinPair<T>* part,
                                                       int64_t* best_idx, T* best_cost) {
-  __shared__ T sv[256];
-  __shared__ int64_t si[256];
   T bv = T(0);
   int64_t bi = -1;
   for (int p = threadIdx.x; p < nparts; p += 256) {
@@ -1262,23 +1157,10 @@ __global__ __launch_bounds__(256) void k_argmin_final(int nparts, const MinPair<
     const int64_t i = part[p].i;
     if (i >= 0 && better(v, i, bv, bi)) { bv = v; bi = i; }
   }
-  sv[threadIdx.x] = bv;
-  si[threadIdx.x] = bi;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      const T ov = sv[threadIdx.x + s];
-      const int64_t oi = si[threadIdx.x + s];
-      if (oi >= 0 && better(ov, oi, sv[threadIdx.x], si[threadIdx.x])) {
-        sv[threadIdx.x] = ov;
-        si[threadIdx.x] = oi;
-      }
-    }
-    __syncthreads();
-  }
+  const MinPair<T> r = block_argmin(bv, bi);
   if (threadIdx.x == 0) {
-    *best_idx = si[0];
-    *best_cost = si[0] >= 0 ? sv[0] : (T)INFINITY;
+    *best_idx = r.i;
+    *best_cost = r.i >= 0 ? r.v : (T)INFINITY;
   }
 }
 
@@ -1322,8 +1204,6 @@ __global__ __launch_bounds__(256) void k_round_pick(int world, int64_t width, in
                                                     int64_t pack_count, const T* cost_all,
                                                     const T* pack_all, T* best_cost, T* winner,
                                                     int64_t* best_global) {
-  __shared__ T sv[256];
-  __shared__ int64_t si[256];
   const int64_t G = (int64_t)world * width;
   T bv = T(0);
   int64_t bi = -1;
@@ -1331,98 +1211,20 @@ __global__ __launch_bounds__(256) void k_round_pick(int world, int64_t width, in
     const T v = cost_all[i];
     if (better(v, i, bv, bi)) { bv = v; bi = i; }
   }
-  sv[threadIdx.x] = bv;
-  si[threadIdx.x] = bi;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      const T ov = sv[threadIdx.x + s];
-      const int64_t oi = si[threadIdx.x + s];
-      if (oi >= 0 && better(ov, oi, sv[threadIdx.x], si[threadIdx.x])) {
-        sv[threadIdx.x] = ov;
-        si[threadIdx.x] = oi;
-      }
-    }
-    __syncthreads();
-  }
-  const int64_t p = si[0];
+  const MinPair<T> r = block_argmin(bv, bi);
+  const int64_t p = r.i;
   const int64_t q = p < 0 ? 0 : p;
   const int64_t owner = q / width, loc = q - owner * width;
   const int64_t base = total / world, rem = total - base * world;
   const int64_t lo = owner * base + (owner < rem ? owner : rem);
   if (threadIdx.x == 0) {
-    *best_cost = p >= 0 ? sv[0] : (T)INFINITY;
+    *best_cost = p >= 0 ? r.v : (T)INFINITY;
     best_global[0] = p < 0 ? -1 : lo + loc;
     best_global[1] = owner;
   }
   for (int64_t e = threadIdx.x; e < pack_count; e += 256)
     winner[e] = pack_all[owner * pack_count + e];
 }
-
-// ---- RCCL, bound at run time ---------------------------------------------------------------
-// The one collective of the path is an all-gather of the candidates' terminal
-// costs.  libi2lqr_hip.so does not link librccl: a process that already carries a copy (PyTorch
-// ships its own librccl.so, the one torch.distributed's "nccl" backend uses) must not get a
-// second one, and single-GPU users need none at all.  The first communicator call looks for a
-// loaded librccl first and loads the ROCm one otherwise.
-struct RcclApi {
-  void* lib = nullptr;
-  ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-  ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*CommAbort)(ncclComm_t) = nullptr;
-  ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;
-  ncclResult_t (*CommUserRank)(const ncclComm_t, int*) = nullptr;
-  ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t,
-                            hipStream_t) = nullptr;
-  ncclResult_t (*Broadcast)(const void*, void*, size_t, ncclDataType_t, int, ncclComm_t,
-                            hipStream_t) = nullptr;
-  ncclResult_t (*GroupStart)() = nullptr;  // optional: without them the two all-gathers of a
-  ncclResult_t (*GroupEnd)() = nullptr;    // round are issued one after the other
-  const char* (*GetErrorString)(ncclResult_t) = nullptr;
-  bool ok = false;
-  char why[256] = "";  // the loader's message, captured once (dlerror() is cleared by reading it)
-};
-
-const RcclApi& rccl_api() {
-  static const RcclApi api = [] {
-    RcclApi a;
-    for (const char* name : {"librccl.so", "librccl.so.1"})
-      if ((a.lib = dlopen(name, RTLD_NOW | RTLD_NOLOAD))) break;
-    if (!a.lib)
-      for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
-        if ((a.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL))) break;
-    if (!a.lib) {
-      const char* e = dlerror();
-      snprintf(a.why, sizeof(a.why), "%s", e ? e : "librccl.so not found by the dynamic loader");
-      return a;
-    }
-    auto sym = [&](const char* n) { return dlsym(a.lib, n); };
-    a.GetUniqueId = (decltype(a.GetUniqueId))sym("ncclGetUniqueId");
-    a.CommInitRank = (decltype(a.CommInitRank))sym("ncclCommInitRank");
-    a.CommDestroy = (decltype(a.CommDestroy))sym("ncclCommDestroy");
-    a.CommAbort = (decltype(a.CommAbort))sym("ncclCommAbort");
-    a.CommCount = (decltype(a.CommCount))sym("ncclCommCount");
-    a.CommUserRank = (decltype(a.CommUserRank))sym("ncclCommUserRank");
-    a.AllGather = (decltype(a.AllGather))sym("ncclAllGather");
-    a.Broadcast = (decltype(a.Broadcast))sym("ncclBroadcast");
-    a.GroupStart = (decltype(a.GroupStart))sym("ncclGroupStart");
-    a.GroupEnd = (decltype(a.GroupEnd))sym("ncclGroupEnd");
-    a.GetErrorString = (decltype(a.GetErrorString))sym("ncclGetErrorString");
-    a.ok = a.GetUniqueId && a.CommInitRank && a.CommDestroy && a.CommAbort && a.CommCount &&
-           a.CommUserRank && a.AllGather && a.Broadcast && a.GetErrorString;
-    if (!a.ok) snprintf(a.why, sizeof(a.why), "the loaded librccl lacks a symbol this library binds");
-    return a;
-  }();
-  return api;
-}
-
-#define RCCL_TRY(api, expr)                                                                 \
-  do {                                                                                      \
-    ncclResult_t r_ = (expr);                                                               \
-    if (r_ != ncclSuccess)                                                                  \
-      return fail(I2LQR_ERR_LAUNCH, "%s failed: %s", #expr, (api).GetErrorString(r_));      \
-  } while (0)
 
 constexpr int kArgminBlocks = 256;
 constexpr int64_t kArgminSingle = 16384;  // up to here a single workgroup scans the vector
@@ -1515,20 +1317,10 @@ int i2lqr_create(const i2lqr_config* cfg, i2lqr_handle** out) {
     return fail(I2LQR_ERR_INVALID, "need dt > 0, lamb_factor > 1, max_iter >= 0");
   for (int a = 0; a < m; a++)
     if (!(cfg->u_max[a] > 0)) return fail(I2LQR_ERR_INVALID, "u_max[%d] must be > 0", a);
-  if (cfg->layout != I2LQR_LAYOUT_PROBLEM_MAJOR) {
-    // the one-problem-per-lane kernels store only the upper triangles of the value function
-    for (int i = 0; i < n; i++)
-      for (int j = 0; j < i; j++)
-        if (cfg->Q[i * I2LQR_MAX_N + j] != cfg->Q[j * I2LQR_MAX_N + i] ||
-            cfg->Qt[i * I2LQR_MAX_N + j] != cfg->Qt[j * I2LQR_MAX_N + i])
-          return fail(I2LQR_ERR_UNSUPPORTED, "the batch-minor / batch-tiled layouts need "
-                      "symmetric Q and Qterminal (use the problem-major layout otherwise)");
-    for (int a = 0; a < m; a++)
-      for (int b = 0; b < a; b++)
-        if (cfg->R[a * I2LQR_MAX_M + b] != cfg->R[b * I2LQR_MAX_M + a])
-          return fail(I2LQR_ERR_UNSUPPORTED, "the batch-minor / batch-tiled layouts need a "
-                      "symmetric R (use the problem-major layout otherwise)");
-  }
+  if (cfg->layout != I2LQR_LAYOUT_PROBLEM_MAJOR)
+    if (const char* what = lane_asymmetry(*cfg))
+      return fail(I2LQR_ERR_UNSUPPORTED, "the batch-minor / batch-tiled layouts need %s (use the "
+                  "problem-major layout otherwise)", what);
   int ndev = 0;
 #ifdef I2LQR_DRY_RUN
   const bool dry_run = dry::on();  // (sanitizer build + I2LQR_DRY_RUN=1: launches are recorded, not run)
@@ -1547,25 +1339,6 @@ int i2lqr_create(const i2lqr_config* cfg, i2lqr_handle** out) {
     return fail(I2LQR_ERR_UNSUPPORTED, "the kernels are built for 64-lane wavefronts (gfx950), this "
                 "device reports %d", w);
   }
-  h->ws = nullptr;
-  h->ws_bytes = 0;
-  h->compact_min_batch = -1;
-  h->opt_defer = h->opt_reroll = h->opt_lds_steps = h->opt_fstep = h->opt_group = -1;
-  h->opt_merge = h->opt_ckpt = h->opt_spec = h->opt_stagger = h->opt_group_ws = -1;
-  h->opt_group_overlap = -1;
-  h->opt_group_fixed = -1;
-  h->opt_ls = 0;
-  h->wave_tail = -1;
-  h->opt_first_chunk = -1;
-  h->opt_fuse = -1;
-  h->opt_final_round = -1;
-  h->opt_chunk_step = -1;
-  h->opt_pair = -1;
-  h->opt_two_x = -1;
-  h->ticket = nullptr;
-  h->ticket_next.store(0);
-  h->ev_ready = h->ev_side_done = nullptr;
-  h->side_pending = false;
   constexpr size_t kTicketBytes = i2lqr_handle::kTickets * sizeof(unsigned);
   if (dry_run) {
 #ifdef I2LQR_DRY_RUN
@@ -1651,26 +1424,12 @@ int64_t i2lqr_workspace_bytes(const i2lqr_handle* h, int64_t B) {
                ? group_workspace_bytes(h->cfg, B) : 0;
   }
   const bool tiled = h->cfg.layout == I2LQR_LAYOUT_BATCH_TILED;
-  const int N = h->cfg.N;
-  const bool f64 = h->cfg.dtype == I2LQR_F64;
-  switch (h->cfg.system_id) {
-    case I2LQR_SYS_BICYCLE4:
-      if (f64) return tiled ? LaneLaunch<double, Bicycle4<double>, true>::ws_bytes(N, B)
-                            : LaneLaunch<double, Bicycle4<double>, false>::ws_bytes(N, B);
-      return tiled ? LaneLaunch<float, Bicycle4<float>, true>::ws_bytes(N, B)
-                   : LaneLaunch<float, Bicycle4<float>, false>::ws_bytes(N, B);
-    case I2LQR_SYS_BICYCLE6:
-      if (f64) return tiled ? LaneLaunch<double, Bicycle6<double>, true>::ws_bytes(N, B)
-                            : LaneLaunch<double, Bicycle6<double>, false>::ws_bytes(N, B);
-      return tiled ? LaneLaunch<float, Bicycle6<float>, true>::ws_bytes(N, B)
-                   : LaneLaunch<float, Bicycle6<float>, false>::ws_bytes(N, B);
-    case I2LQR_SYS_QUAD12:
-      if (f64) return tiled ? LaneLaunch<double, Quad12<double>, true>::ws_bytes(N, B)
-                            : LaneLaunch<double, Quad12<double>, false>::ws_bytes(N, B);
-      return tiled ? LaneLaunch<float, Quad12<float>, true>::ws_bytes(N, B)
-                   : LaneLaunch<float, Quad12<float>, false>::ws_bytes(N, B);
-    default: return 0;
-  }
+  return visit_plant(h->cfg, [&](auto t, auto sys) {
+    using T = decltype(t);
+    using Sys = decltype(sys);
+    return tiled ? LaneLaunch<T, Sys, true>::ws_bytes(h->cfg.N, B)
+                 : LaneLaunch<T, Sys, false>::ws_bytes(h->cfg.N, B);
+  });
 }
 
 // Batch sizes from which the one-problem-per-lane layouts win over the problem-major kernels.
@@ -1727,14 +1486,7 @@ int i2lqr_recommended_layout(const i2lqr_config* cfg, int64_t B, int32_t early_e
   // what the lane layouts cannot run stays problem-major: non-symmetric weights (the kernels keep
   // the upper triangles), and for quad12 (row-block kernel) fp32 WITH stage weights
   const bool weights = has_stage_weights(*cfg);
-  bool lane_ok = true;
-  for (int i = 0; i < cfg->n; i++)
-    for (int j = 0; j < cfg->n; j++)
-      if (cfg->Q[i * I2LQR_MAX_N + j] != cfg->Q[j * I2LQR_MAX_N + i] ||
-          cfg->Qt[i * I2LQR_MAX_N + j] != cfg->Qt[j * I2LQR_MAX_N + i]) lane_ok = false;
-  for (int a = 0; a < cfg->m; a++)
-    for (int b = 0; b < cfg->m; b++)
-      if (cfg->R[a * I2LQR_MAX_M + b] != cfg->R[b * I2LQR_MAX_M + a]) lane_ok = false;
+  bool lane_ok = !lane_asymmetry(*cfg);
   int64_t from;
   switch (cfg->system_id) {
     case I2LQR_SYS_BICYCLE4:
@@ -1951,14 +1703,11 @@ int i2lqr_relax_cost(i2lqr_handle* h, int64_t B, const void* X, const void* x_te
   const unsigned grid = (unsigned)((B + 255) / 256);
   const int bm = h->cfg.layout;  // 0 problem-major, 1 batch-minor, 2 batch-tiled
   hipStream_t s = (hipStream_t)stream;
-  if (h->cfg.dtype == I2LQR_F64)
-    hipLaunchKernelGGL((k_relax_cost<double>), dim3(grid), dim3(256), 0, s, B, h->cfg.n, h->cfg.N,
-                       bm, (const double*)X, (const double*)x_term, qfun, outer_iter, max_relax_iter,
-                       (double*)cost_it);
-  else
-    hipLaunchKernelGGL((k_relax_cost<float>), dim3(grid), dim3(256), 0, s, B, h->cfg.n, h->cfg.N,
-                       bm, (const float*)X, (const float*)x_term, qfun, outer_iter, max_relax_iter,
-                       (float*)cost_it);
+  visit_precision(h->cfg, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_relax_cost<T>), dim3(grid), dim3(256), 0, s, B, h->cfg.n, h->cfg.N, bm,
+                       (const T*)X, (const T*)x_term, qfun, outer_iter, max_relax_iter, (T*)cost_it);
+  });
   HIP_TRY(hipGetLastError());
   return I2LQR_OK;
 }
@@ -1982,28 +1731,19 @@ int i2lqr_argmin(i2lqr_handle* h, int64_t B, const void* cost_it, int64_t* best_
   hipStream_t s = (hipStream_t)stream;
   int64_t want = (B + 255) / 256;
   const int blocks = (int)(want < 1 ? 1 : (want > kArgminBlocks ? kArgminBlocks : want));
-  if (B <= kArgminSingle) {  // one workgroup, one launch
-    if (h->cfg.dtype == I2LQR_F64)
-      hipLaunchKernelGGL((k_argmin_partial<double, true>), dim3(1), dim3(256), 0, s, B,
-                         (const double*)cost_it, (MinPair<double>*)nullptr, best_idx,
-                         (double*)best_cost);
-    else
-      hipLaunchKernelGGL((k_argmin_partial<float, true>), dim3(1), dim3(256), 0, s, B,
-                         (const float*)cost_it, (MinPair<float>*)nullptr, best_idx,
-                         (float*)best_cost);
-  } else if (h->cfg.dtype == I2LQR_F64) {
-    auto* part = (MinPair<double>*)workspace;
-    hipLaunchKernelGGL((k_argmin_partial<double>), dim3(blocks), dim3(256), 0, s, B,
-                       (const double*)cost_it, part);
-    hipLaunchKernelGGL((k_argmin_final<double>), dim3(1), dim3(256), 0, s, blocks, part, best_idx,
-                       (double*)best_cost);
-  } else {
-    auto* part = (MinPair<float>*)workspace;
-    hipLaunchKernelGGL((k_argmin_partial<float>), dim3(blocks), dim3(256), 0, s, B,
-                       (const float*)cost_it, part);
-    hipLaunchKernelGGL((k_argmin_final<float>), dim3(1), dim3(256), 0, s, blocks, part, best_idx,
-                       (float*)best_cost);
-  }
+  visit_precision(h->cfg, [&](auto t) {
+    using T = decltype(t);
+    auto* part = (MinPair<T>*)workspace;
+    if (B <= kArgminSingle) {  // one workgroup, one launch
+      hipLaunchKernelGGL((k_argmin_partial<T, true>), dim3(1), dim3(256), 0, s, B, (const T*)cost_it,
+                         (MinPair<T>*)nullptr, best_idx, (T*)best_cost);
+    } else {
+      hipLaunchKernelGGL((k_argmin_partial<T>), dim3(blocks), dim3(256), 0, s, B, (const T*)cost_it,
+                         part);
+      hipLaunchKernelGGL((k_argmin_final<T>), dim3(1), dim3(256), 0, s, blocks, part, best_idx,
+                         (T*)best_cost);
+    }
+  });
   HIP_TRY(hipGetLastError());
   return I2LQR_OK;
 }
@@ -2063,14 +1803,11 @@ int i2lqr_select_candidates(i2lqr_handle* h, int32_t L, int32_t Tmax, const void
   if (!ss || !T || !qfun || !x_guess || !idx || !x_term || !qf)
     return fail(I2LQR_ERR_INVALID, "null buffer");
   hipStream_t s = (hipStream_t)stream;
-  if (h->cfg.dtype == I2LQR_F64)
-    hipLaunchKernelGGL((k_select_candidates<double>), dim3(L), dim3(128), 0, s, h->cfg.n, Tmax, k,
-                       (const double*)ss, T, qfun, (const double*)x_guess, guess_stride, idx,
-                       (double*)x_term, qf);
-  else
-    hipLaunchKernelGGL((k_select_candidates<float>), dim3(L), dim3(128), 0, s, h->cfg.n, Tmax, k,
-                       (const float*)ss, T, qfun, (const float*)x_guess, guess_stride, idx,
-                       (float*)x_term, qf);
+  visit_precision(h->cfg, [&](auto t) {
+    using R = decltype(t);  // (T: the laps' column counts)
+    hipLaunchKernelGGL((k_select_candidates<R>), dim3(L), dim3(128), 0, s, h->cfg.n, Tmax, k,
+                       (const R*)ss, T, qfun, (const R*)x_guess, guess_stride, idx, (R*)x_term, qf);
+  });
   HIP_TRY(hipGetLastError());
   return I2LQR_OK;
 }
@@ -2084,12 +1821,11 @@ int i2lqr_init_candidates(i2lqr_handle* h, int64_t B, const void* x0, double lam
   if (!x0 || !X || !U || !lamb) return fail(I2LQR_ERR_INVALID, "null buffer");
   hipStream_t s = (hipStream_t)stream;
   const int n = h->cfg.n, m = h->cfg.m, N = h->cfg.N;
-  if (h->cfg.dtype == I2LQR_F64)
-    hipLaunchKernelGGL((k_init_candidates<double>), dim3((unsigned)B), dim3(64), 0, s, B, n, m, N,
-                       (const double*)x0, lamb0, (double*)X, (double*)U, (double*)lamb);
-  else
-    hipLaunchKernelGGL((k_init_candidates<float>), dim3((unsigned)B), dim3(64), 0, s, B, n, m, N,
-                       (const float*)x0, (float)lamb0, (float*)X, (float*)U, (float*)lamb);
+  visit_precision(h->cfg, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_init_candidates<T>), dim3((unsigned)B), dim3(64), 0, s, B, n, m, N,
+                       (const T*)x0, (T)lamb0, (T*)X, (T*)U, (T*)lamb);
+  });
   HIP_TRY(hipGetLastError());
   return I2LQR_OK;
 }
@@ -2108,14 +1844,11 @@ int i2lqr_pick_best(i2lqr_handle* h, int32_t L, int32_t k, const void* cost_it, 
     return fail(I2LQR_ERR_UNSUPPORTED, "controller-round kernels need the problem-major layout");
   hipStream_t s = (hipStream_t)stream;
   const int n = h->cfg.n, m = h->cfg.m, N = h->cfg.N;
-  if (h->cfg.dtype == I2LQR_F64)
-    hipLaunchKernelGGL((k_pick_best<double>), dim3(1), dim3(64), 0, s, L, k, n, m, N,
-                       (const double*)cost_it, (const double*)X, (const double*)U, best,
-                       (double*)x_pred, (double*)u_pred);
-  else
-    hipLaunchKernelGGL((k_pick_best<float>), dim3(1), dim3(64), 0, s, L, k, n, m, N,
-                       (const float*)cost_it, (const float*)X, (const float*)U, best,
-                       (float*)x_pred, (float*)u_pred);
+  visit_precision(h->cfg, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_pick_best<T>), dim3(1), dim3(64), 0, s, L, k, n, m, N, (const T*)cost_it,
+                       (const T*)X, (const T*)U, best, (T*)x_pred, (T*)u_pred);
+  });
   HIP_TRY(hipGetLastError());
   return I2LQR_OK;
 }
@@ -2234,12 +1967,11 @@ int i2lqr_pack_problem(i2lqr_handle* h, int64_t B, const void* X, const void* U,
     return fail(I2LQR_ERR_INVALID, "the batch-tiled layout needs a batch that is a multiple of 64");
   hipStream_t s = (hipStream_t)stream;
   const int n = h->cfg.n, m = h->cfg.m, N = h->cfg.N;
-  if (h->cfg.dtype == I2LQR_F64)
-    hipLaunchKernelGGL((k_pack_problem<double>), dim3(1), dim3(256), 0, s, B, n, m, N,
-                       (int)h->cfg.layout, (const double*)X, (const double*)U, idx, (double*)pack);
-  else
-    hipLaunchKernelGGL((k_pack_problem<float>), dim3(1), dim3(256), 0, s, B, n, m, N,
-                       (int)h->cfg.layout, (const float*)X, (const float*)U, idx, (float*)pack);
+  visit_precision(h->cfg, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_pack_problem<T>), dim3(1), dim3(256), 0, s, B, n, m, N, (int)h->cfg.layout,
+                       (const T*)X, (const T*)U, idx, (T*)pack);
+  });
   HIP_TRY(hipGetLastError());
   return I2LQR_OK;
 }
@@ -2254,14 +1986,11 @@ int i2lqr_round_winner(i2lqr_handle* h, int32_t world, int64_t width, int64_t to
   if (!best_padded || !best_global || (pack_count > 0 && (!pack_all || !winner)))
     return fail(I2LQR_ERR_INVALID, "null buffer");
   hipStream_t s = (hipStream_t)stream;
-  if (h->cfg.dtype == I2LQR_F64)
-    hipLaunchKernelGGL((k_round_winner<double>), dim3(1), dim3(256), 0, s, world, width, total,
-                       pack_count, best_padded, (const double*)pack_all, (double*)winner,
-                       best_global);
-  else
-    hipLaunchKernelGGL((k_round_winner<float>), dim3(1), dim3(256), 0, s, world, width, total,
-                       pack_count, best_padded, (const float*)pack_all, (float*)winner,
-                       best_global);
+  visit_precision(h->cfg, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((k_round_winner<T>), dim3(1), dim3(256), 0, s, world, width, total, pack_count,
+                       best_padded, (const T*)pack_all, (T*)winner, best_global);
+  });
   HIP_TRY(hipGetLastError());
   return I2LQR_OK;
 }
@@ -2295,14 +2024,12 @@ int i2lqr_round_pick(i2lqr_handle* h, int32_t world, int64_t width, int64_t tota
     return fail(I2LQR_ERR_INVALID, "null buffer");
   hipStream_t s = (hipStream_t)stream;
   if (G <= kArgminSingle) {
-    if (h->cfg.dtype == I2LQR_F64)
-      hipLaunchKernelGGL((k_round_pick<double>), dim3(1), dim3(256), 0, s, world, width, total,
-                         pack_count, (const double*)cost_all, (const double*)pack_all,
-                         (double*)best_cost, (double*)winner, best_global);
-    else
-      hipLaunchKernelGGL((k_round_pick<float>), dim3(1), dim3(256), 0, s, world, width, total,
-                         pack_count, (const float*)cost_all, (const float*)pack_all,
-                         (float*)best_cost, (float*)winner, best_global);
+    visit_precision(h->cfg, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((k_round_pick<T>), dim3(1), dim3(256), 0, s, world, width, total, pack_count,
+                         (const T*)cost_all, (const T*)pack_all, (T*)best_cost, (T*)winner,
+                         best_global);
+    });
     HIP_TRY(hipGetLastError());
     return I2LQR_OK;
   }
@@ -2393,16 +2120,13 @@ int i2lqr_sharded_round_flat(i2lqr_handle* h, void* comm, const i2lqr_round* r, 
   {
     int64_t padblocks = ragged ? (width + 255) / 256 : 1;
     if (padblocks > 64) padblocks = 64;
-    if (h->cfg.dtype == I2LQR_F64)
-      hipLaunchKernelGGL((k_round_prepare<double>), dim3((unsigned)padblocks), dim3(256), 0, ss, r->B,
-                         n, m, N, (int)h->cfg.layout, (const double*)r->X, (const double*)r->U,
-                         r->local_best, (double*)r->pack_local, width, (const double*)r->cost_it,
-                         ragged ? (double*)r->cost_padded : (double*)nullptr);
-    else
-      hipLaunchKernelGGL((k_round_prepare<float>), dim3((unsigned)padblocks), dim3(256), 0, ss, r->B,
-                         n, m, N, (int)h->cfg.layout, (const float*)r->X, (const float*)r->U,
-                         r->local_best, (float*)r->pack_local, width, (const float*)r->cost_it,
-                         ragged ? (float*)r->cost_padded : (float*)nullptr);
+    visit_precision(h->cfg, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL((k_round_prepare<T>), dim3((unsigned)padblocks), dim3(256), 0, ss, r->B, n,
+                         m, N, (int)h->cfg.layout, (const T*)r->X, (const T*)r->U, r->local_best,
+                         (T*)r->pack_local, width, (const T*)r->cost_it,
+                         ragged ? (T*)r->cost_padded : (T*)nullptr);
+    });
     HIP_TRY(hipGetLastError());
   }
   const void* src = ragged ? r->cost_padded : r->cost_it;

@@ -29,6 +29,11 @@ inline int stage_weight_flags(const i2lqr_config& h, int n, int m) {
 // true if the configuration has stage weights (Q or R != 0): DevCfg::flags != 0
 inline bool has_stage_weights(const i2lqr_config& h) { return stage_weight_flags(h, h.n, h.m) != 0; }
 
+// f(T()) for the precision a (validated) configuration names
+template <class F> auto visit_precision(const i2lqr_config& cfg, F&& f) {
+  if (cfg.dtype == I2LQR_F64) return f(double());
+  return f(float());
+}
 // f(T(), Sys()) for the plant and precision a (validated) configuration names; T fixes the
 // precision instead.  visit_bicycle: the two m = 2 plants (any other system id: bicycle6).
 template <class T = void, class F> auto visit_bicycle(const i2lqr_config& cfg, F&& f) {
