@@ -16,6 +16,7 @@ MAX_N = 12
 MAX_M = 4
 MAX_HORIZON = 64
 OBS_WORDS = 6
+MAX_OBSTACLES = 8  # I2LQR_MAX_OBSTACLES: records per problem with the "obstacles" option
 COMM_ID_BYTES = 128
 QF_NONE = 0x7FFFFFFF  # I2LQR_QF_NONE: qfun value of an empty candidate slot
 

@@ -28,7 +28,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .params import X_DIM, U_DIM, config_from_params, obstacle_record
+from .params import X_DIM, U_DIM, ObstacleSet, config_from_params, obstacle_record
 
 
 class ControlBase:
@@ -90,7 +90,8 @@ class iLqr(ControlBase):
                              "device_rounds: the chain kernel and the device rounds have no line search")
         self.ilqr_param = ilqr_param
         self.system_param = system_param
-        self.obstacle = obstacle          # public: scenario scripts swap it between laps
+        self.obstacle = obstacle          # public: scenario scripts swap it between laps (an
+        #                                   Obstacle, None, or an ObstacleSet of up to 8)
         self.lamb_mode = lamb_mode
         self.device_rounds = device_rounds
         self.verbose = verbose
@@ -259,6 +260,11 @@ class iLqr(ControlBase):
         """utils/base.py:371-479."""
         p = self.ilqr_param
         num_horizon = self.num_horizon
+        if (self.device_rounds or self.sharded is not None) and \
+                isinstance(self.obstacle, ObstacleSet) and len(self.obstacle) > 1:
+            raise ValueError("an ObstacleSet of more than one (the \"obstacles\" option) runs without "
+                             "device_rounds and sharded=: those rounds read one obstacle record per "
+                             "problem")
         min_iter = np.max([0, self.iter - p.num_ss_iter])
         rounds = []
         if self.num_horizon < p.num_horizon:

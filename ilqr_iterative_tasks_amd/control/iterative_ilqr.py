@@ -22,7 +22,12 @@ class HipCandidateSolver:
     line_search = 2, 4 or 8: every handle is created problem-major, whatever layout the library
     recommends for the batch, with the "line_search" option set (include/i2lqr.h: that many step
     sizes 2^-j per iteration on k_iterate_ls — not the reference's algorithm); independent lamb
-    only, solve_chained raises."""
+    only, solve_chained raises.
+
+    An obstacle record of shape (K, 6) with K > 1 (params.obstacle_record of an ObstacleSet) is K
+    obstacles per problem — not the reference's model: solve() and solve_chained() (a launch per
+    chain step) then run on a problem-major handle with the "obstacles" option set to K
+    (k_iterate_obs); candidate_round / sharded_round raise."""
 
     def __init__(self, device="cuda:0", dtype="f64", line_search=1):
         if int(line_search) not in (-1, 0, 1, 2, 4, 8):
@@ -32,12 +37,30 @@ class HipCandidateSolver:
         self.line_search = int(line_search) if int(line_search) > 1 else 1
         self._solvers = {}
 
-    def _solver(self, cfg, B=None, early_exit=True):
+    @staticmethod
+    def _obs_records(obs_rec):
+        """(record array or None, K): (6,) and K = 1 for one obstacle, (K, 6) for K > 1."""
+        if obs_rec is None:
+            return None, 1
+        rec = np.asarray(obs_rec, float)
+        if rec.ndim == 2 and rec.shape[0] == 1:
+            rec = rec[0]
+        if rec.shape[-1] != 6 or rec.ndim > 2:
+            raise ValueError(f"obstacle record of shape {rec.shape}: expected (6,) or (K, 6)")
+        return rec, (rec.shape[0] if rec.ndim == 2 else 1)
+
+    def _refuse_obstacles(self, obs_rec, what):
+        if self._obs_records(obs_rec)[1] > 1:
+            raise ValueError(f"{what}: built for one obstacle record per problem; with the "
+                             "\"obstacles\" option (an ObstacleSet of more than one) use solve() or "
+                             "solve_chained()")
+
+    def _solver(self, cfg, B=None, early_exit=True, n_obs=1):
         """The handle for this configuration; with B given, in the layout the LIBRARY recommends
         for batches of that size (i2lqr_recommended_layout): a caller who hands 65536 candidates
         to solve() gets the one-problem-per-lane kernels without knowing that they exist."""
         from ..solver import BatchedILQR
-        if self.line_search > 1:  # k_iterate_ls is a problem-major kernel
+        if self.line_search > 1 or n_obs > 1:  # k_iterate_ls / k_iterate_obs are problem-major kernels
             if cfg.layout != 0:
                 cfg = cfg.copy()
                 cfg.layout = 0
@@ -46,11 +69,13 @@ class HipCandidateSolver:
             if lay != cfg.layout:
                 cfg = cfg.copy()
                 cfg.layout = lay
-        key = bytes(C.string_at(C.byref(cfg), C.sizeof(cfg)))
+        key = bytes(C.string_at(C.byref(cfg), C.sizeof(cfg))) + bytes([n_obs if n_obs > 1 else 0])
         if key not in self._solvers:
             self._solvers[key] = BatchedILQR(cfg, self.device)
             if self.line_search > 1:
                 self._solvers[key].set_option("line_search", self.line_search)
+            if n_obs > 1:
+                self._solvers[key].set_option("obstacles", n_obs)
         return self._solvers[key]
 
     def _round_buffers(self, cfg, x0, x_terms, qfun, lamb0, obs_rec, early_exit):
@@ -102,6 +127,7 @@ class HipCandidateSolver:
         Returns device tensors: cost_it[B], best_idx[1] (int64), best_cost[1] and the winner's
         U[m, N], X[n, N+1]; `solver` / `buf` (the layout the library chose and the full batch in
         it) ride along for callers that want more than the winner."""
+        self._refuse_obstacles(obs_rec, "candidate_round")
         solver, buf, qfun, cost_it = self._round_buffers(cfg, x0, x_terms, qfun, lamb0, obs_rec,
                                                          n_iters is None)
         idx, val = self._solve_and_cost(solver, buf, qfun, cost_it, n_iters, outer_iter,
@@ -158,6 +184,7 @@ class HipCandidateSolver:
         behind the shard's solve, then (host-driven form) see dist.flat_round / lexi_round."""
         from .. import dist as idist
         import torch
+        self._refuse_obstacles(obs_rec, "sharded_round")
         if int(total) < 1:  # (every rank knows `total`: all raise together, before any collective)
             raise ValueError("a sharded round needs at least one candidate over all ranks")
         on_phase = on_phase or (lambda name: None)
@@ -264,11 +291,12 @@ class HipCandidateSolver:
         return res
 
     def solve(self, cfg, x0, x_terms, lamb0, obs_rec, U0=None):
-        """x0[n] (shared) or [B,n]; x_terms[B,n]; lamb0[B]; obs_rec[6] (shared) or None.
+        """x0[n] (shared) or [B,n]; x_terms[B,n]; lamb0[B]; obs_rec[6] or [K,6] (shared) or None.
         Returns dict(U[B,m,N], X[B,n,N+1], lamb[B], iters[B], status[B], cost[B]) on the host."""
         x_terms = np.atleast_2d(np.asarray(x_terms, float))
         B = x_terms.shape[0]
-        solver = self._solver(cfg, B, early_exit=True)
+        obs_rec, K = self._obs_records(obs_rec)
+        solver = self._solver(cfg, B, early_exit=True, n_obs=K)
         if not (solver.batch_minor or solver.batch_tiled) and B <= 4096:
             return self._solve_packed(solver, cfg, B, x0, x_terms, lamb0, obs_rec, U0)
         return self._solve_generic(solver, cfg, B, x0, x_terms, lamb0, obs_rec, U0)
@@ -281,6 +309,7 @@ class HipCandidateSolver:
         cost ten fills and eleven transfers per call: 150 us against 45)."""
         import torch
         n, m, N = cfg.n, cfg.m, cfg.N
+        osh = (B, 6) if solver.obstacles == 1 else (B, solver.obstacles, 6)
         key = (id(solver), B, obs_rec is not None)
         if not hasattr(self, "_packs"):
             self._packs = {}
@@ -291,7 +320,7 @@ class HipCandidateSolver:
             item = 8 if solver.dtype == torch.float64 else 4
             npdt = np.float64 if item == 8 else np.float32
             sizes = [("X", B * n * (N + 1)), ("U", B * m * N), ("x_term", B * n), ("lamb", B),
-                     ("obs", B * 6), ("cost", B)]
+                     ("obs", int(np.prod(osh))), ("cost", B)]
             off, o = {}, 0
             for name, cnt in sizes:
                 off[name] = (o, cnt)
@@ -309,7 +338,7 @@ class HipCandidateSolver:
                     "status": dev[ioff + step:ioff + step + B * 4].view(torch.int32)}
             buf = dict(X=dview["X"].view(B, n, N + 1), U=dview["U"].view(B, m, N),
                        x_term=dview["x_term"].view(B, n), lamb=dview["lamb"], cost=dview["cost"],
-                       obs=dview["obs"].view(B, 6) if obs_rec is not None else None,
+                       obs=dview["obs"].view(osh) if obs_rec is not None else None,
                        iters=dint["iters"], status=dint["status"], K=None, k=None)
             pk = self._packs[key] = dict(host=host, dev=dev, h=hview, hi=hint, buf=buf,
                                          in_bytes=off["cost"][0], npdt=npdt)
@@ -322,7 +351,7 @@ class HipCandidateSolver:
         h["x_term"].reshape(B, n)[:] = x_terms
         h["lamb"][:] = np.asarray(lamb0, float).reshape(B)
         if obs_rec is not None:
-            h["obs"].reshape(B, 6)[:] = np.asarray(obs_rec, float)
+            h["obs"].reshape(osh)[:] = np.asarray(obs_rec, float)
         nb = pk["in_bytes"]
         pk["dev"][:nb].copy_(pk["host"][:nb], non_blocking=True)
         solver.solve(pk["buf"])
@@ -357,11 +386,13 @@ class HipCandidateSolver:
         rows = [[a for a, w in enumerate(widths) if c < w] for c in range(width)]
         counts = [len(r) for r in rows]
         B = sum(counts)
-        solver = self._solver(cfg, max(counts), early_exit=True)
+        obs_rec, n_obs = self._obs_records(obs_rec)
+        solver = self._solver(cfg, max(counts), early_exit=True, n_obs=n_obs)
         if solver.batch_minor or solver.batch_tiled or B > 4096:
             raise ValueError("solve_chained is the controller's path: problem-major batches")
         n, m, N = cfg.n, cfg.m, cfg.N
         has_obs = obs_rec is not None
+        osh = (B, 6) if solver.obstacles == 1 else (B, solver.obstacles, 6)
         key = ("chain", id(solver), tuple(widths), has_obs)
         if not hasattr(self, "_packs"):
             self._packs = {}
@@ -371,7 +402,7 @@ class HipCandidateSolver:
                 self._packs.clear()
             item = 8 if solver.dtype == torch.float64 else 4
             sizes = [("X", B * n * (N + 1)), ("U", B * m * N), ("x_term", B * n), ("lamb", B),
-                     ("obs", B * 6), ("cost", B)]
+                     ("obs", int(np.prod(osh))), ("cost", B)]
             off, o = {}, 0
             for name, cnt in sizes:
                 off[name] = (o, cnt)
@@ -395,7 +426,7 @@ class HipCandidateSolver:
                 steps.append(dict(
                     X=dv["X"].view(B, n, N + 1)[lo:hi_], U=dv["U"].view(B, m, N)[lo:hi_],
                     x_term=dv["x_term"].view(B, n)[lo:hi_], lamb=dv["lamb"][lo:hi_],
-                    cost=dv["cost"][lo:hi_], obs=dv["obs"].view(B, 6)[lo:hi_] if has_obs else None,
+                    cost=dv["cost"][lo:hi_], obs=dv["obs"].view(osh)[lo:hi_] if has_obs else None,
                     iters=di["iters"][lo:hi_], status=di["status"][lo:hi_], K=None, k=None))
             # where step c's chains sat in step c - 1 (chains only ever drop out: ordered subsets)
             gather = [None]
@@ -417,7 +448,7 @@ class HipCandidateSolver:
                 xt[starts[c] + r] = chains[a][c]
         h["lamb"][:] = float(lamb0)  # (steps behind the first get theirs on the device)
         if has_obs:
-            h["obs"].reshape(B, 6)[:] = np.asarray(obs_rec, float)
+            h["obs"].reshape(osh)[:] = np.asarray(obs_rec, float)
         nb = pk["in_bytes"]
         if pk.get("one_launch") is None:
             pk["one_launch"] = len(set(widths)) == 1 and getattr(self, "use_chain_kernel", True)
@@ -426,7 +457,7 @@ class HipCandidateSolver:
                 whole = {name: torch.as_strided(first[name], (B,) + tuple(first[name].shape[1:]),
                                                 first[name].stride(), first[name].storage_offset())
                          for name in ("X", "U", "x_term", "lamb", "cost", "iters", "status")}
-                whole["obs"] = (torch.as_strided(first["obs"], (B, 6), first["obs"].stride(),
+                whole["obs"] = (torch.as_strided(first["obs"], osh, first["obs"].stride(),
                                                  first["obs"].storage_offset()) if has_obs else None)
                 whole["K"] = whole["k"] = None
                 pk["whole"] = whole
@@ -510,7 +541,8 @@ class HipCandidateSolver:
         buf["x_term"].copy_(dev(x_terms))
         buf["lamb"].copy_(dev(np.asarray(lamb0, float).reshape(B)))
         if obs_rec is not None:
-            buf["obs"] = dev(np.tile(np.asarray(obs_rec, float), (B, 1)))
+            rec = np.asarray(obs_rec, float)
+            buf["obs"] = dev(np.broadcast_to(rec, (B,) + rec.shape))
         solver.solve(buf)
         host = lambda t: solver.to_problem_major(t).double().cpu().numpy()
         return dict(U=host(buf["U"]), X=host(buf["X"]), lamb=host(buf["lamb"]),
@@ -562,7 +594,7 @@ def ilqr(ilqr_param, num_horizon, xtarget, timestep, obstacle, system_param, x_t
     cfg = config_from_params(ilqr_param, system_param, num_horizon, timestep, xtarget)
     x0 = np.array(np.asarray(xvar, float)[:, 0])
     U0 = np.array(uvar, float)
-    obs = None if obstacle is None else obstacle_record(obstacle)
+    obs = None if obstacle is None else obstacle_record(obstacle)  # (an ObstacleSet: (K, 6))
     out = solver.solve(cfg, x0, np.asarray(x_terminal, float)[None], [float(lamb)], obs,
                        U0=U0[None])
     if int(ilqr_param.max_ilqr_iter) > 0 and isinstance(uvar, np.ndarray) and \

@@ -51,6 +51,35 @@ class Obstacle:
         self.states = np.array([self.x0, self.y0])
 
 
+class ObstacleSet:
+    """Several obstacles per problem (the "obstacles" option of include/i2lqr.h; not the reference's
+    model, which takes one).  Stands where an Obstacle stands: update_obstacle() / reset_obstacle()
+    go to every member, iteration yields the members, obstacle_record() gives the (K, 6) records.
+    A set of one behaves exactly as its Obstacle."""
+
+    def __init__(self, obstacles):
+        self.obstacles = list(obstacles)
+        if not self.obstacles:
+            raise ValueError("an ObstacleSet needs at least one Obstacle (use None for no obstacle)")
+        if len(self.obstacles) > _abi.MAX_OBSTACLES:
+            raise ValueError(f"an ObstacleSet holds at most {_abi.MAX_OBSTACLES} obstacles "
+                             f"(\"obstacles\" option), got {len(self.obstacles)}")
+
+    def __iter__(self):
+        return iter(self.obstacles)
+
+    def __len__(self):
+        return len(self.obstacles)
+
+    def update_obstacle(self):
+        for o in self.obstacles:
+            o.update_obstacle()
+
+    def reset_obstacle(self):
+        for o in self.obstacles:
+            o.reset_obstacle()
+
+
 class iLqrParam:
     def __init__(self, matrix_Q=0 * np.diag([0.0, 0.0, 0.0, 0.0]),
                  matrix_R=0 * np.diag([0.05, 0.05]),
@@ -93,7 +122,11 @@ class iLqrParam:
 def obstacle_record(obstacle) -> np.ndarray:
     """Reference Obstacle (or None) -> the 6-word obs record of include/i2lqr.h.  The reference
     raises NameError for spd != 0 with moving_option None (control/ilqr_helper.py:34-43); that
-    combination is rejected here instead."""
+    combination is rejected here instead.  An ObstacleSet gives its members' records, shape (K, 6);
+    a set of one the record of its Obstacle, shape (6,)."""
+    if isinstance(obstacle, ObstacleSet):
+        recs = np.stack([obstacle_record(o) for o in obstacle])
+        return recs[0] if len(recs) == 1 else recs
     if obstacle is None:
         return np.array([0.0, 0.0, 1.0, 1.0, 0.0, -1.0])
     spd = 0.0 if obstacle.spd is None else float(obstacle.spd)

@@ -23,6 +23,7 @@
 #include "i2lqr_rccl.hpp"
 #include "i2lqr_select.hpp"
 #include "i2lqr_wave_ls.h"
+#include "i2lqr_wave_obs.h"
 
 #define I2LQR_DRY_RUN_LANE 1
 #include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
@@ -168,6 +169,7 @@ struct i2lqr_handle {
   int opt_spec = -1;   // eight-lane kernel: speculative form (2-3 wavefronts per eight problems); -1 = automatic
   int opt_group_ws = -1;  // eight-lane kernel: workspace form (records / gains in HBM); -1 = automatic
   int opt_group_overlap = -1;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; -1 = automatic (on)
+  int opt_obs = 0;  // one-problem-per-wavefront kernel: obstacle records per problem (k_iterate_obs): 2 ... I2LQR_MAX_OBSTACLES; 0: off (one record)
   int opt_ls = 0;  // one-problem-per-wavefront kernel: step sizes of the parallel line search (k_iterate_ls): 2, 4, 8; 0: off
   int opt_group_fixed = -1;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; -1 = automatic (on)
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
@@ -205,7 +207,7 @@ namespace {
 
 // Which fused kernel a problem-major call runs on: ONE function, used by the launchers and by
 // i2lqr_iterate_kernel / i2lqr_solve_kernel (what bench.py labels its results with).
-enum FusedKernel { K_WAVE, K_WAVE_LS, K_GROUP, K_GROUP16, K_GROUP_WS, K_SPEC, K_SPEC16, K_QUAD, K_INVALID };
+enum FusedKernel { K_WAVE, K_WAVE_LS, K_WAVE_OBS, K_GROUP, K_GROUP16, K_GROUP_WS, K_SPEC, K_SPEC16, K_QUAD, K_INVALID };
 // (measured on the 256-CU chip; DeviceGeometry::scaled() elsewhere)
 constexpr int64_t kAutoGroupBatch = 1024;  // eight-lane kernel from here (automatic)
 constexpr int64_t kAutoSpecBatch = 12288;  // speculative form for solves up to here (automatic)
@@ -214,6 +216,16 @@ constexpr int64_t kAutoSpecBatch = 12288;  // speculative form for solves up to 
 FusedKernel select_fused(const i2lqr_handle* h, int64_t B, bool early_exit, const char** why) {
   static const char* none = "";
   if (!why) why = &none;
+  // "obstacles": every call runs on the several-obstacles form of the one-problem-per-wavefront
+  // kernel (k_iterate_obs, i2lqr_wave_obs.hip), whatever the batch size; it carries the line search
+  if (h->opt_obs > 1) {
+    if (h->opt_group == 8 || h->opt_group == 16) {
+      *why = "\"obstacles\" runs on the one-problem-per-wavefront kernel: not together with "
+             "\"group_lanes\" = 8 or 16";
+      return K_INVALID;
+    }
+    return K_WAVE_OBS;
+  }
   // "line_search": every call runs on the line-search form of the one-problem-per-wavefront kernel
   // (k_iterate_ls, i2lqr_wave_ls.hip), whatever the batch size
   if (h->opt_ls > 1) {
@@ -431,6 +443,15 @@ template <class T, class Sys> struct Launch {
           return I2LQR_OK;
         }
         break;
+      case K_WAVE_OBS:
+        if (h->lds_bytes + wave_obs_lds_bytes(h->opt_obs, sizeof(T)) > h->geo.max_dyn_lds)
+          return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d with \"obstacles\" = %d needs %zu B of LDS "
+                      "per wavefront (> %zu KiB)", h->cfg.N, h->opt_obs,
+                      h->lds_bytes + wave_obs_lds_bytes(h->opt_obs, sizeof(T)),
+                      h->geo.max_dyn_lds / 1024);
+        HIP_TRY(wave_obs_iterate<T>(h->cfg, a, h->opt_ls > 1 ? h->opt_ls : 1, h->opt_obs,
+                                    h->lds_bytes, s));
+        return I2LQR_OK;
       case K_WAVE_LS:
         HIP_TRY(wave_ls_iterate<T>(h->cfg, a, h->opt_ls, h->lds_bytes, s));
         return I2LQR_OK;
@@ -1565,6 +1586,15 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
                   "one-problem-per-wavefront kernel)");
     h->opt_ls = v > 1 ? v : 0;
   }
+  else if (!strcmp(name, "obstacles")) {
+    if (v > I2LQR_MAX_OBSTACLES)
+      return fail(I2LQR_ERR_INVALID, "\"obstacles\" is 2 ... %d records per problem, or -1 / 0 / 1 "
+                  "(off: one record)", I2LQR_MAX_OBSTACLES);
+    if (v > 1 && h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR)
+      return fail(I2LQR_ERR_UNSUPPORTED, "\"obstacles\" is built for the problem-major layout (the "
+                  "one-problem-per-wavefront kernel)");
+    h->opt_obs = v > 1 ? v : 0;
+  }
   else if (!strcmp(name, "group_lanes")) {
     if (v != -1 && v != 8 && v != 16 && v != 64)
       return fail(I2LQR_ERR_INVALID, "\"group_lanes\" is 8, 16, 64 or -1");
@@ -1592,6 +1622,7 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
     case K_GROUP16: return "k_group_iterate (sixteen lanes)";
     case K_GROUP_WS: return "k_group_iterate (workspace form)";
     case K_QUAD: return "k_quad_iterate";
+    case K_WAVE_OBS: return "k_iterate (several obstacles)";
     case K_WAVE_LS: return "k_iterate (line search)";
     case K_WAVE: return "k_iterate";
     default: return "unsupported";  // the launch returns I2LQR_ERR_UNSUPPORTED
@@ -1626,6 +1657,9 @@ int i2lqr_backward(i2lqr_handle* h, int64_t B, const void* X, const void* U, con
   if (int rc = check_common(h, B)) return rc;
   if (B == 0) return I2LQR_OK;
   if (!X || !U || !x_term || !lamb || !K || !k) return fail(I2LQR_ERR_INVALID, "null buffer");
+  if (h->opt_obs > 1)
+    return fail(I2LQR_ERR_UNSUPPORTED, "i2lqr_backward reads one obstacle record per problem: "
+                "switch \"obstacles\" off, or use i2lqr_iterate");
   const int rc = dispatch(h, [&](auto L) {
     return L.backward(h, B, X, U, x_term, lamb, obs, K, k, (hipStream_t)stream);
   });
@@ -1681,6 +1715,10 @@ int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void
   if (!X || !U || !x_term || !lamb || !cost) return fail(I2LQR_ERR_INVALID, "null buffer");
   if ((K == nullptr) != (k == nullptr))
     return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
+  if (h->opt_obs > 1)
+    return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which reads "
+                "one obstacle record per problem: switch \"obstacles\" off, or solve the chain steps "
+                "one after the other");
   if (h->opt_ls > 1)
     return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which has "
                 "no line search: switch \"line_search\" off, or solve the chain steps one after the "

@@ -47,6 +47,7 @@ class BatchedILQR:
         self.batch_minor = cfg.layout == _abi.LAYOUT_BATCH_MINOR
         self.batch_tiled = cfg.layout == _abi.LAYOUT_BATCH_TILED
         self._ws = None  # scratch of the batch-minor kernels (registered on the handle)
+        self.obstacles = 1  # obstacle records per problem ("obstacles" option: 2 ... 8)
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc: int) -> None:
@@ -85,8 +86,9 @@ class BatchedILQR:
     # -- layout ---------------------------------------------------------------------------------
     def shape(self, name: str, B: int) -> tuple:
         n, m, N = self.n, self.m, self.N
+        n_obs = getattr(self, "obstacles", 1)  # ("obstacles" option: K > 1 records per problem)
         core = {"X": (n, N + 1), "U": (m, N), "K": (m, n, N), "k": (m, N), "x_term": (n,),
-                "obs": (OBS_WORDS,), "lamb": (), "cost": (), "iters": (), "status": (),
+                "obs": (n_obs, OBS_WORDS) if n_obs > 1 else (OBS_WORDS,), "lamb": (), "cost": (), "iters": (), "status": (),
                 "qfun": (), "cost_it": ()}[name]
         if (self.batch_minor or self.batch_tiled) and len(core) >= 2:
             core = core[-1:] + core[:-1]  # the lane layouts are time-major
@@ -151,9 +153,13 @@ class BatchedILQR:
         """Scheduling options (i2lqr_set_option in include/i2lqr.h); -1 restores the automatic
         choice.  Lane layouts: "defer_states", "reroll_nominal", "lds_gain_steps", "wave_tail";
         problem-major layout: "group_lanes" (8 / 16 / 64), "speculate", "per_step_jacobians",
-        "line_search" (2 / 4 / 8 step sizes per iteration on k_iterate_ls; 0 off).  All but
-        "wave_tail", "group_lanes" and "line_search" leave the results bit-identical."""
+        "line_search" (2 / 4 / 8 step sizes per iteration on k_iterate_ls; 0 off), "obstacles"
+        (K = 2 ... 8 obstacle records per problem on k_iterate_obs: `obs` is then [B, K, 6] and
+        shape("obs", B) says so; 0 off).  All but "wave_tail", "group_lanes", "line_search" and
+        "obstacles" leave the results bit-identical."""
         self._check(self.lib.i2lqr_set_option(self._handle, name.encode(), int(value)))
+        if name == "obstacles":
+            self.obstacles = int(value) if int(value) > 1 else 1
 
     def iterate_kernel(self, B: int) -> str:
         """Name of the kernel iterate() launches for B problems (rocprofv3 traces)."""

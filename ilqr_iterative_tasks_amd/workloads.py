@@ -114,6 +114,36 @@ def make_batch(cfg: I2lqrConfig, B: int, seed: int = SEED, offset: int = 0,
     return dict(X=X, U=np.zeros((B, m, N)), x_term=x, lamb=np.ones(B), obs=obs)
 
 
+def obstacles_on_path(host: dict, K: int, seed: int = SEED, options=None) -> np.ndarray:
+    """obs[B, K, 6] for the "obstacles" option (include/i2lqr.h), placed where they matter: record j
+    of a problem sits on the problem's own straight line from x0 to x_term at the fraction
+    (j + 1) / (K + 1), moved sideways by a seeded offset of up to half its size, so every record
+    bends its problem's trajectory (make_batch's fixed obstacle at x = 31 touches only the few
+    problems of a random batch that start near it).  Records are a mix of static, moving up
+    (option 1) and moving left (option 2): record j of problem b has option (b + j) mod 3, or
+    options[j] for every problem where `options` (K values) is given.  Sizes and speeds follow the
+    plant's scale: bicycles (n <= 6) semi-axes (3, 2) m and 0.2 m per step, quad12 (0.5, 0.5) and
+    0.005."""
+    x0, xT = np.asarray(host["X"])[:, :2, 0], np.asarray(host["x_term"])[:, :2]
+    B = x0.shape[0]
+    quad = np.asarray(host["X"]).shape[1] > 6
+    w, h, spd = (0.5, 0.5, 0.005) if quad else (3.0, 2.0, 0.2)
+    rng = np.random.default_rng([seed, K, 7])
+    d = xT - x0
+    length = np.linalg.norm(d, axis=1)
+    along = np.where(length[:, None] > 0, d / np.maximum(length, 1e-300)[:, None], [[1.0, 0.0]])
+    side = np.stack([-along[:, 1], along[:, 0]], axis=1)
+    obs = np.zeros((B, K, 6))
+    for j in range(K):
+        off = rng.uniform(-0.5, 0.5, B) * h
+        obs[:, j, :2] = x0 + d * ((j + 1) / (K + 1)) + side * off[:, None]
+        obs[:, j, 2], obs[:, j, 3] = w, h
+        opt = (np.arange(B) + j) % 3 if options is None else np.full(B, int(options[j]))
+        obs[:, j, 4] = np.where(opt > 0, spd, 0.0)
+        obs[:, j, 5] = opt
+    return obs
+
+
 def algorithmic_bytes_per_iteration(cfg: I2lqrConfig) -> int:
     """compulsory HBM bytes per iLQR iteration per problem if the state
     round-trips HBM once per iteration: read X, U, x_term, lamb; write X', U', K, k, cost, lamb.

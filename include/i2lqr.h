@@ -51,6 +51,7 @@ extern "C" {
 #define I2LQR_MAX_M 4
 #define I2LQR_MAX_HORIZON 64
 #define I2LQR_OBS_WORDS 6
+#define I2LQR_MAX_OBSTACLES 8 /* records per problem with the "obstacles" option */
 #define I2LQR_QF_NONE 0x7fffffff /* qfun value of an empty candidate slot (i2lqr_select_candidates) */
 
 /* cfg.dtype */
@@ -354,6 +355,24 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     default: the iteration above with one step is the reference's).  Any other
  *                     value is I2LQR_ERR_INVALID; a batch-minor / batch-tiled handle answers
  *                     I2LQR_ERR_UNSUPPORTED to 2, 4 or 8.
+ *   "obstacles"       2 ... I2LQR_MAX_OBSTACLES (8): K = value obstacle records per problem — NOT the
+ *                     reference's model (control/ilqr_helper.py takes one obstacle).  The obs argument
+ *                     of i2lqr_iterate / i2lqr_solve (and of i2lqr_iterate_pick, which takes its
+ *                     unfused form) is then obs[B][K][6]: each record the six words above;
+ *                     moving_option < 0 disables that record, a NULL obs all of them.  Each record
+ *                     contributes exactly the single obstacle's barrier terms (stage index t,
+ *                     terminal index N, moving options 1 and 2, safety_margin, obs_q1 / obs_q2) to
+ *                     l_x, l_xx, V_x, V_xx; the contributions are summed in record order starting from
+ *                     the first enabled record's value, so a problem with one enabled record computes
+ *                     that obstacle's single-record numbers.  Backward pass, forward pass and accept /
+ *                     reject (whose cost has no barrier term) are unchanged.  While it is on EVERY
+ *                     call of the handle, whatever the batch size, runs on k_iterate_obs — one
+ *                     problem per wavefront (three plants, both precisions, with or without stage
+ *                     weights); together with "line_search" every iteration also tries that
+ *                     option's step sizes.  i2lqr_backward, i2lqr_solve_chained and a forced
+ *                     "group_lanes" 8 or 16 answer I2LQR_ERR_UNSUPPORTED.  -1, 0 or 1: off (the
+ *                     default: obs[B][6]).  Any other value is I2LQR_ERR_INVALID; a batch-minor /
+ *                     batch-tiled handle answers I2LQR_ERR_UNSUPPORTED to 2 ... 8.
  *   "stagger"         lane layouts (k_lane_iterate_rows, k_lane_iterate): every second half-thousand
  *                     of workgroups starts value x ~8000 cycles late, so that half of the
  *                     wavefronts stream their gains (forward pass) while the other half computes
@@ -370,7 +389,7 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
 int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value);
 
 /* Name of the kernel i2lqr_iterate (fixed iteration count) launches for a batch of B problems
- * with the handle's current options: "k_iterate", "k_iterate (line search)", "k_group_iterate", "k_group_iterate (sixteen
+ * with the handle's current options: "k_iterate", "k_iterate (line search)", "k_iterate (several obstacles)", "k_group_iterate", "k_group_iterate (sixteen
  * lanes)", "k_group_iterate (workspace form)", "k_group_spec", "k_group_spec (sixteen lanes)",
  * "k_quad_iterate", "k_lane_iterate", "k_lane_iterate_pair" (the helper-wavefront form),
  * "k_lane_iterate_rows"; "unsupported" if a forced option cannot be honoured and the launch would

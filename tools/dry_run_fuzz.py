@@ -47,7 +47,7 @@ OPTIONS = {"defer_states": (0, 1), "reroll_nominal": (0, 1), "lds_gain_steps": (
            "first_chunk": (1, 4, 8, 12, 150), "helper_wavefront": (0, 1), "state_buffers": (0, 1),
            "chunk_step": (1, 2, 4, 9), "speculate": (0, 1), "group_workspace": (0, 1),
            "group_lanes": (8, 16, 64), "fused_compaction": (0, 1), "final_round": (0, 1, 2, 3, 5),
-           "line_search": (0, 2, 4, 8)}
+           "line_search": (0, 2, 4, 8), "obstacles": (0, 2, 3, 8)}
 
 
 class Arena:
@@ -237,15 +237,18 @@ for it in range(args.configs):
     if rc != 0:
         stats["refused"] += 1
         continue
+    n_obs = 1  # records per problem: obs[B][n_obs][6] once "obstacles" is accepted
     for name in rng.choice(list(OPTIONS), size=int(rng.integers(0, 5)), replace=False):
-        lib.i2lqr_set_option(h, name.encode(), int(rng.choice(OPTIONS[name])))
+        value = int(rng.choice(OPTIONS[name]))
+        if lib.i2lqr_set_option(h, name.encode(), value) == 0 and name == "obstacles":
+            n_obs = max(value, 1)
     if rng.random() < 0.2:
         lib.i2lqr_set_compaction(h, int(rng.choice([0, 64, 4096])))
     item = 8 if dtype == "f64" else 4
     n, m = cfg.n, cfg.m
     arena = Arena()
     X, U = arena.take(B * n * (N + 1) * item), arena.take(B * m * N * item)
-    xt, lamb, obs = arena.take(B * n * item), arena.take(B * item), arena.take(B * 6 * item)
+    xt, lamb, obs = arena.take(B * n * item), arena.take(B * item), arena.take(B * n_obs * 6 * item)
     cost, K, k = arena.take(B * item), arena.take(B * m * n * N * item), arena.take(B * m * N * item)
     iters, status = arena.take(B * 4), arena.take(B * 4)
     X2, U2, c2 = arena.take(B * n * (N + 1) * item), arena.take(B * m * N * item), arena.take(B * item)
