@@ -1802,7 +1802,7 @@ __global__ __launch_bounds__(64, (sizeof(T) == 4 ? I2LQR_F32_WAVES : I2LQR_F64_W
   const LaneView<TILED> v(a.B);
   if (a.resume && a.status[b] != 0) {  // finished since the compaction (tail kernel)
     // fused compaction: what a tail kernel finished without delivering it goes to the caller now
-    if (a.cp.on && true)
+    if (a.cp.on)
       lane_exit_compact(a.cp, n, m, N, b, v.Bs, v.bl, v.rebase(a.X, n * (N + 1)),
                         v.rebase(a.U, m * N), v.rebase(a.x_term, n), v.rebase(a.obs, 6),
                         v.rebase(a.K ? a.K : a.wsK, m * n * N), v.rebase(a.K ? a.k : a.wsk, m * N),
@@ -2004,14 +2004,8 @@ __global__ __launch_bounds__(128, 1) void k_lane_iterate_pair(
   T lamb = a.lamb[b];
   T* gK = v.rebase(a.K ? a.K : a.wsK, m * n * N);
   T* gk = v.rebase(a.K ? a.k : a.wsk, m * N);
-  // States live in ONE buffer (the caller's X); only the inputs (m N words) are double-buffered
-  // per lane.  With X double-buffered per lane too, divergent accept/reject decisions split every
-  // row access of a wavefront over two buffers: +38 % HBM traffic per iteration (rocprofv3
-  // FETCH_SIZE / WRITE_SIZE, tools/pmc_iters.sh).  Either the forward pass stores no states and
-  // accepted steps re-roll them (a.defer), or it writes the candidate states over the nominal
-  // ones in place (each x_t is loaded one step ahead of being overwritten) and rejected steps
-  // re-roll the nominal ones; both re-rolls are bit-identical to what the rollout stored.
-  // THIS kernel runs launches of at most 512 workgroups, bound by the instruction stream of a step
+  // One state buffer, two input buffers per lane, deferred or in-place candidate states: see
+  // k_lane_iterate.  THIS kernel runs launches of at most 512 workgroups, bound by the instruction stream of a step
   // and not by HBM: with a second state buffer in the workspace (a.wsX; the host passes one up to
   // 256 workgroups) the forward pass stores the candidate states there and an accepted lane swaps
   // its state and input buffers — no re-roll (15 % of an iteration of the main wavefront at 16384
@@ -2024,11 +2018,7 @@ __global__ __launch_bounds__(128, 1) void k_lane_iterate_pair(
   const bool two = a.wsX != nullptr && live <= a.two_max;
   T *X = X0, *Xn = two ? v.rebase(a.wsX, n * (N + 1)) : X0;
 
-  // The nominal rollout of iteration i+1 is bit-identical to the forward rollout of an accepted
-  // iteration i (same inputs, same code), and unchanged after a rejected one: roll out once.
-  // checkpointed states (fp64 only; host: deferred + merged + re-rolling forward pass, Q = R = 0)
-  constexpr bool kCanCkpt = false;  // (the host gives this kernel no checkpointed launch)
-  const bool ckpt = false;
+  // (states are not checkpointed here: the host gives this kernel no checkpointed launch)
   // LDS behind the gains: the two record slots and the control words of the pair
   typedef LaneWorker<T, Sys, HASQR, TILED> LW;
   w.rec = (lds_t*)lane_smem + (size_t)a.lds_steps * 64 * m * (n + 1) + 64 * m;
@@ -2049,12 +2039,11 @@ __global__ __launch_bounds__(128, 1) void k_lane_iterate_pair(
   if (a.stagger > 0 && ((blockIdx.x >> 9) & 1)) {  // see k_lane_iterate_rows
     for (int q = 0; q < a.stagger; q++) __builtin_amdgcn_s_sleep(127);
   }
-  T cost = w.rollout(X, Uc, xT, ckpt);
+  T cost = w.rollout(X, Uc, xT);
   const int it0 = a.resume ? a.iters[b] : 0;  // iterations of earlier chunks
   int it = 0, status = a.early_exit ? 2 : 0;
   T cost_ret = cost;
   while (it < a.n_iters && it0 + it < a.max_total) {
-    // K_0 goes to HBM from the passes that can be this launch's last one for the problem
     const bool k0_out = a.early_exit || it + 1 >= a.n_iters || it0 + it + 1 >= a.max_total;
     ctl[l64] = (Uc != U0 ? 1 : 0) | (X != X0 ? 2 : 0);  // where this lane's nominal trajectory is
     ctl[64] = 1;
@@ -2086,35 +2075,18 @@ __global__ __launch_bounds__(128, 1) void k_lane_iterate_pair(
 #endif
     it++;
     const bool accepted = cost_new < cost;
-    // X must hold the states of each lane's CURRENT inputs: deferred mode owes them to the lanes
-    // that accepted, in-place mode to the lanes that rejected.  If any lane of the wavefront needs
-    // it, ALL of them re-roll and store (the others rewrite what is already there, bit for bit):
-    // full 64-lane rows instead of masked partial ones, which cost a read-modify-write in HBM.
+    // the state restore of k_lane_iterate (see there), unless the lane has a second state buffer
     if (two) {
       if (accepted) {
         T* tp = Uc; Uc = Un; Un = tp;
         tp = X; X = Xn; Xn = tp;
       }
     } else if (a.defer && a.merge) {
-      // the current inputs stay in ONE buffer for the whole wavefront: accepted candidates are
-      // merged into it during the re-roll (Uc == U0, Un == workspace throughout)
       if (__all(accepted)) {
-        // every lane of the wavefront accepted: the two input buffers change roles for the whole
-        // wavefront (still ONE buffer with full rows, no copy) and the states are re-rolled
         T* tp = Uc; Uc = Un; Un = tp;
-        if constexpr (kCanCkpt) {
-          if (ckpt) w.template restore_states_paired<false, true>(X, Uc);
-          else w.restore_states(X, Uc);
-        } else {
-          w.restore_states(X, Uc);
-        }
+        w.restore_states(X, Uc);
       } else if (__any(accepted)) {
-        if constexpr (kCanCkpt) {
-          if (ckpt) w.template merge_and_restore<true>(X, Uc, Un, accepted);
-          else w.merge_and_restore(X, Uc, Un, accepted);
-        } else {
-          w.merge_and_restore(X, Uc, Un, accepted);
-        }
+        w.merge_and_restore(X, Uc, Un, accepted);
       }
     } else {
       if (accepted) {
@@ -2156,9 +2128,6 @@ __global__ __launch_bounds__(128, 1) void k_lane_iterate_pair(
   if (a.dbg && threadIdx.x == 0)
     for (int q = 0; q < 8; q++) a.dbg[blockIdx.x * 8 + q] = w.st_acc[q];
 #endif
-  if constexpr (kCanCkpt) {
-    if (ckpt) w.restore_states(X, Uc);  // the caller's X in full: one re-roll per launch
-  }
   w.flush_gains(gK, gk);
   // the accepted trajectory sits in the workspace: copy it out, 32 rows in flight at a time (one
   // row per round trip to HBM was 44 us of a 0.46 ms launch)

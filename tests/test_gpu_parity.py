@@ -667,6 +667,38 @@ def test_chunked_compacting_solve_is_bit_identical_to_plain(torch_mod, lay, dtyp
     assert torch.equal(b2["iters"][:sub], r2["iters"])
 
 
+@pytest.mark.parametrize("lay,B", [("tiled", 192), ("lane", 131)])
+def test_quad12_chunked_solve_on_the_lane_layouts_is_bit_identical_to_plain(torch_mod, lay, B):
+    """The row-block kernel (k_lane_iterate_rows) as a chunk of the chunked solve: it enters with
+    the iteration counts of the earlier chunks, skips what has terminated since and leaves through
+    the compaction, fused into its exit or as a launch of its own.  Three wavefronts on the
+    batch-tiled layout, two and a ragged tail on the batch-minor one; chunks of two iterations,
+    no tail kernel.  Every output must equal, bit for bit, the single launch of the same handle."""
+    torch = torch_mod
+    from ilqr_iterative_tasks_amd import workloads
+    solver, cfg = make_solver("quad12", 10, "f64", dt=0.02, layout=lay)
+    assert solver.solve_kernel(B) == "k_lane_iterate_rows"
+    host = workloads.make_batch(cfg, B)
+    host["lamb"] = 10.0 ** np.random.default_rng(4).integers(-3, 3, B).astype(float)
+    solver.set_compaction(0)
+    plain = solver.solve(dev_batch(solver, host))
+    check_solve_outputs(solver, cfg, host, plain)
+    it = plain["iters"].cpu().numpy()
+    # chunks of two iterations: a problem with more than four enters a third chunk (so max_iter is
+    # above the first chunk too, without which set_compaction(64) would take the single launch)
+    assert cfg.max_iter > 4 and B >= 64
+    assert it.max() > 4 and len(np.unique(it)) > 2, "several chunks, problems leaving in each"
+    solver.set_compaction(64)
+    solver.set_option("wave_tail", 0)
+    solver.set_option("first_chunk", 2)
+    solver.set_option("chunk_step", 2)
+    for fused in (1, 0):
+        solver.set_option("fused_compaction", fused)
+        got = solver.solve(dev_batch(solver, host))
+        for key in ("X", "U", "K", "k", "lamb", "cost", "iters", "status"):
+            assert torch.equal(got[key], plain[key]), (key, fused)
+
+
 def test_edge_cases(torch_mod, layout):
     torch = torch_mod
     from ilqr_iterative_tasks_amd import workloads
