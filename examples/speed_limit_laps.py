@@ -1,0 +1,63 @@
+#!/usr/bin/env python3
+"""Closed-loop i2LQR laps of the reference's static-obstacle scenario (iterative_ilqr/tests/
+ilqr_test.py:81-92; obstacle (31, -3, 8, 6)) with a SPEED LIMIT:
+
+    python examples/speed_limit_laps.py --v-max 8 --lap-number 3
+
+The reference carries v_min / v_max (KineticBicycleParam) and tuning_state_q1 / q2 (iLqrParam) and
+reads them nowhere: its laps go 121 / 54 / 29 / 23 steps whatever v_max says.  Here
+state_box_from_params turns them into a box on the state v, and every candidate is solved with that
+box (i2lqr_set_state_box of include/i2lqr.h, k_iterate_box; with chained lamb one launch per chain
+step): 121 / 54 / 32 / 32 steps at v in [0, 8].  The barrier is soft, as the input barrier is: the
+top speed of a controlled lap ends near 9, not at 8.  --no-limit runs the free loop.
+"""
+import argparse
+import sys
+from pathlib import Path
+
+import numpy as np
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+from ilqr_iterative_tasks_amd import harness
+from ilqr_iterative_tasks_amd.control import (KineticBicycleParam, Obstacle, iLqr, iLqrParam,
+                                              state_box_from_params)
+from ilqr_iterative_tasks_amd.control.iterative_ilqr import HipCandidateSolver
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--v-min", type=float, default=0.0)
+    ap.add_argument("--v-max", type=float, default=8.0)
+    ap.add_argument("--q1", type=float, default=1.0, help="tuning_state_q1")
+    ap.add_argument("--q2", type=float, default=1.0, help="tuning_state_q2")
+    ap.add_argument("--no-limit", action="store_true")
+    ap.add_argument("--lap-number", type=int, default=3)
+    ap.add_argument("--num-ss-points", type=int, default=8)
+    ap.add_argument("--num-ss-iters", type=int, default=2)
+    ap.add_argument("--lamb-mode", default="chained", choices=["chained", "independent"])
+    args = ap.parse_args()
+
+    dt = 1
+    system = KineticBicycleParam(v_min=args.v_min, v_max=args.v_max)
+    ego = harness.KineticBicycle(system_param=system)
+    ego.set_state(np.zeros(4))
+    ego.set_timestep(dt)
+    ego.get_traj()
+    ego.set_zero_noise()
+    param = iLqrParam(num_ss_points=args.num_ss_points, num_ss_iter=args.num_ss_iters, timestep=dt,
+                      num_horizon=6, tuning_state_q1=args.q1, tuning_state_q2=args.q2)
+    box = None if args.no_limit else state_box_from_params(system, param)
+    ctrl = iLqr(param, obstacle=Obstacle(31, -3, 8, 6), system_param=system,
+                solver=HipCandidateSolver(state_box=box), lamb_mode=args.lamb_mode)
+    ctrl.add_trajectory(ego.xcl, ego.ucl)
+    ctrl.set_timestep(dt)
+    ego.set_ctrl_policy(ctrl)
+    laps = harness.run_laps(ego, ctrl, args.lap_number)
+    print("time at iteration 0 is", laps[0] * dt, " s")
+    for lap, steps in enumerate(laps[1:], 1):
+        top = float(np.asarray(ego.data["state"][lap - 1])[:, 2].max())
+        print("time at iteration ", lap, " is ", steps * dt, " s, top speed", round(top, 2))
+
+
+if __name__ == "__main__":
+    main()

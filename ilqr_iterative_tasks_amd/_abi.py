@@ -184,6 +184,7 @@ EXPORTS = {
     "i2lqr_set_workspace": (C.c_int, [_P, _P, C.c_int64]),
     "i2lqr_set_compaction": (C.c_int, [_P, C.c_int64]),
     "i2lqr_set_option": (C.c_int, [_P, C.c_char_p, C.c_int64]),
+    "i2lqr_set_state_box": (C.c_int, [_P, _P, _P, C.c_double, C.c_double]),
     "i2lqr_iterate_kernel": (C.c_char_p, [_P, C.c_int64]),
     "i2lqr_solve_kernel": (C.c_char_p, [_P, C.c_int64]),
     "i2lqr_rollout": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P]),

@@ -88,6 +88,9 @@ class iLqr(ControlBase):
         if getattr(solver, "line_search", 1) > 1 and (lamb_mode == "chained" or device_rounds):
             raise ValueError("a solver with line_search > 1 is for lamb_mode=\"independent\" without "
                              "device_rounds: the chain kernel and the device rounds have no line search")
+        if getattr(solver, "state_box", None) is not None and device_rounds:
+            raise ValueError("a solver with a state box runs without device_rounds: the device rounds "
+                             "have no state box")
         self.ilqr_param = ilqr_param
         self.system_param = system_param
         self.obstacle = obstacle          # public: scenario scripts swap it between laps (an

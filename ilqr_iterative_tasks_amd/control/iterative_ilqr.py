@@ -27,14 +27,20 @@ class HipCandidateSolver:
     An obstacle record of shape (K, 6) with K > 1 (params.obstacle_record of an ObstacleSet) is K
     obstacles per problem — not the reference's model: solve() and solve_chained() (a launch per
     chain step) then run on a problem-major handle with the "obstacles" option set to K
-    (k_iterate_obs); candidate_round / sharded_round raise."""
+    (k_iterate_obs); candidate_round / sharded_round raise.
 
-    def __init__(self, device="cuda:0", dtype="f64", line_search=1):
+    state_box = a params.StateBox with a finite bound (not the reference's model either): every
+    handle is created problem-major and gets the box (i2lqr_set_state_box, k_iterate_box);
+    solve() and solve_chained() (a launch per chain step) work, candidate_round / sharded_round
+    raise."""
+
+    def __init__(self, device="cuda:0", dtype="f64", line_search=1, state_box=None):
         if int(line_search) not in (-1, 0, 1, 2, 4, 8):
             raise ValueError(f"line_search is 2, 4 or 8 step sizes, or -1 / 0 / 1 (off): got {line_search}")
         self.device = device
         self.dtype = dtype
         self.line_search = int(line_search) if int(line_search) > 1 else 1
+        self.state_box = state_box if state_box is not None and state_box.active else None
         self._solvers = {}
 
     @staticmethod
@@ -55,12 +61,18 @@ class HipCandidateSolver:
                              "\"obstacles\" option (an ObstacleSet of more than one) use solve() or "
                              "solve_chained()")
 
+    def _refuse_state_box(self, what):
+        if self.state_box is not None:
+            raise ValueError(f"{what}: has no state box; with a state box use solve() or "
+                             "solve_chained()")
+
     def _solver(self, cfg, B=None, early_exit=True, n_obs=1):
         """The handle for this configuration; with B given, in the layout the LIBRARY recommends
         for batches of that size (i2lqr_recommended_layout): a caller who hands 65536 candidates
         to solve() gets the one-problem-per-lane kernels without knowing that they exist."""
         from ..solver import BatchedILQR
-        if self.line_search > 1 or n_obs > 1:  # k_iterate_ls / k_iterate_obs are problem-major kernels
+        # k_iterate_ls / k_iterate_obs / k_iterate_box are problem-major kernels
+        if self.line_search > 1 or n_obs > 1 or self.state_box is not None:
             if cfg.layout != 0:
                 cfg = cfg.copy()
                 cfg.layout = 0
@@ -70,12 +82,19 @@ class HipCandidateSolver:
                 cfg = cfg.copy()
                 cfg.layout = lay
         key = bytes(C.string_at(C.byref(cfg), C.sizeof(cfg))) + bytes([n_obs if n_obs > 1 else 0])
+        if self.state_box is not None:
+            key += self.state_box.key()
         if key not in self._solvers:
             self._solvers[key] = BatchedILQR(cfg, self.device)
             if self.line_search > 1:
                 self._solvers[key].set_option("line_search", self.line_search)
             if n_obs > 1:
                 self._solvers[key].set_option("obstacles", n_obs)
+            if self.state_box is not None:
+                b = self.state_box
+                if b.lo.size != cfg.n:
+                    raise ValueError(f"the state box has {b.lo.size} components, the plant {cfg.n}")
+                self._solvers[key].set_state_box(b.lo, b.hi, b.q1, b.q2)
         return self._solvers[key]
 
     def _round_buffers(self, cfg, x0, x_terms, qfun, lamb0, obs_rec, early_exit):
@@ -128,6 +147,7 @@ class HipCandidateSolver:
         U[m, N], X[n, N+1]; `solver` / `buf` (the layout the library chose and the full batch in
         it) ride along for callers that want more than the winner."""
         self._refuse_obstacles(obs_rec, "candidate_round")
+        self._refuse_state_box("candidate_round")
         solver, buf, qfun, cost_it = self._round_buffers(cfg, x0, x_terms, qfun, lamb0, obs_rec,
                                                          n_iters is None)
         idx, val = self._solve_and_cost(solver, buf, qfun, cost_it, n_iters, outer_iter,
@@ -185,6 +205,7 @@ class HipCandidateSolver:
         from .. import dist as idist
         import torch
         self._refuse_obstacles(obs_rec, "sharded_round")
+        self._refuse_state_box("sharded_round")
         if int(total) < 1:  # (every rank knows `total`: all raise together, before any collective)
             raise ValueError("a sharded round needs at least one candidate over all ranks")
         on_phase = on_phase or (lambda name: None)

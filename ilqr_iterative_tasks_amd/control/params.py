@@ -80,6 +80,43 @@ class ObstacleSet:
             o.reset_obstacle()
 
 
+class StateBox:
+    """A box on the states (i2lqr_set_state_box of include/i2lqr.h; not the reference's model, which
+    reads its v_min / v_max nowhere): lo[n], hi[n] with -inf / +inf where there is no bound, and the
+    barrier's two tuning scalars.  Soft: the barrier enters the backward pass's derivatives only."""
+
+    def __init__(self, lo, hi, q1=1.0, q2=1.0):
+        self.lo = np.array(lo, dtype=float).ravel()
+        self.hi = np.array(hi, dtype=float).ravel()
+        self.q1, self.q2 = float(q1), float(q2)
+        if self.lo.shape != self.hi.shape or self.lo.size < 1 or self.lo.size > _abi.MAX_N:
+            raise ValueError(f"a StateBox holds one lo and one hi per state component (1 ... "
+                             f"{_abi.MAX_N}), got {self.lo.shape} and {self.hi.shape}")
+        if np.isnan(self.lo).any() or np.isnan(self.hi).any():
+            raise ValueError("a StateBox bound is NaN")
+        if (self.lo >= self.hi).any():
+            raise ValueError(f"a StateBox needs lo < hi in every component, got {self.lo} / {self.hi}")
+        if not (0 < self.q1 < np.inf and 0 < self.q2 < np.inf):
+            raise ValueError(f"a StateBox needs q1, q2 > 0, got {q1}, {q2}")
+
+    @property
+    def active(self) -> bool:
+        """Some bound is finite."""
+        return bool(np.isfinite(self.lo).any() or np.isfinite(self.hi).any())
+
+    def key(self) -> bytes:
+        return self.lo.tobytes() + self.hi.tobytes() + np.array([self.q1, self.q2]).tobytes()
+
+
+def state_box_from_params(system_param, ilqr_param) -> StateBox:
+    """v in [v_min, v_max] (utils/base.py:15-20) on component 2 of the reference plant with
+    tuning_state_q1 / tuning_state_q2 (utils/base.py:242-302): the parameters the reference carries
+    and reads nowhere.  Never applied by default: hand the result to HipCandidateSolver(state_box=)."""
+    lo, hi = np.full(X_DIM, -np.inf), np.full(X_DIM, np.inf)
+    lo[X_ID["v"]], hi[X_ID["v"]] = float(system_param.v_min), float(system_param.v_max)
+    return StateBox(lo, hi, ilqr_param.tuning_state_q1, ilqr_param.tuning_state_q2)
+
+
 class iLqrParam:
     def __init__(self, matrix_Q=0 * np.diag([0.0, 0.0, 0.0, 0.0]),
                  matrix_R=0 * np.diag([0.05, 0.05]),

@@ -23,6 +23,7 @@
 #include "i2lqr_rccl.hpp"
 #include "i2lqr_select.hpp"
 #include "i2lqr_wave_ls.h"
+#include "i2lqr_wave_box.h"
 #include "i2lqr_wave_obs.h"
 
 #define I2LQR_DRY_RUN_LANE 1
@@ -170,6 +171,7 @@ struct i2lqr_handle {
   int opt_group_ws = -1;  // eight-lane kernel: workspace form (records / gains in HBM); -1 = automatic
   int opt_group_overlap = -1;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; -1 = automatic (on)
   int opt_obs = 0;  // one-problem-per-wavefront kernel: obstacle records per problem (k_iterate_obs): 2 ... I2LQR_MAX_OBSTACLES; 0: off (one record)
+  i2lqr::StateBox box;  // one-problem-per-wavefront kernel: the state box (k_iterate_box, i2lqr_set_state_box); box.on(): some bound is finite
   int opt_ls = 0;  // one-problem-per-wavefront kernel: step sizes of the parallel line search (k_iterate_ls): 2, 4, 8; 0: off
   int opt_group_fixed = -1;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; -1 = automatic (on)
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
@@ -207,7 +209,7 @@ namespace {
 
 // Which fused kernel a problem-major call runs on: ONE function, used by the launchers and by
 // i2lqr_iterate_kernel / i2lqr_solve_kernel (what bench.py labels its results with).
-enum FusedKernel { K_WAVE, K_WAVE_LS, K_WAVE_OBS, K_GROUP, K_GROUP16, K_GROUP_WS, K_SPEC, K_SPEC16, K_QUAD, K_INVALID };
+enum FusedKernel { K_WAVE, K_WAVE_LS, K_WAVE_OBS, K_WAVE_BOX, K_GROUP, K_GROUP16, K_GROUP_WS, K_SPEC, K_SPEC16, K_QUAD, K_INVALID };
 // (measured on the 256-CU chip; DeviceGeometry::scaled() elsewhere)
 constexpr int64_t kAutoGroupBatch = 1024;  // eight-lane kernel from here (automatic)
 constexpr int64_t kAutoSpecBatch = 12288;  // speculative form for solves up to here (automatic)
@@ -216,6 +218,17 @@ constexpr int64_t kAutoSpecBatch = 12288;  // speculative form for solves up to 
 FusedKernel select_fused(const i2lqr_handle* h, int64_t B, bool early_exit, const char** why) {
   static const char* none = "";
   if (!why) why = &none;
+  // a state box (i2lqr_set_state_box): every call runs on the state-box form of the
+  // one-problem-per-wavefront kernel (k_iterate_box, i2lqr_wave_box.hip), whatever the batch size; it
+  // carries the obstacle records and the line search
+  if (h->box.on()) {
+    if (h->opt_group == 8 || h->opt_group == 16) {
+      *why = "a state box runs on the one-problem-per-wavefront kernel: not together with "
+             "\"group_lanes\" = 8 or 16";
+      return K_INVALID;
+    }
+    return K_WAVE_BOX;
+  }
   // "obstacles": every call runs on the several-obstacles form of the one-problem-per-wavefront
   // kernel (k_iterate_obs, i2lqr_wave_obs.hip), whatever the batch size; it carries the line search
   if (h->opt_obs > 1) {
@@ -443,6 +456,17 @@ template <class T, class Sys> struct Launch {
           return I2LQR_OK;
         }
         break;
+      case K_WAVE_BOX: {
+        const int n_obs = h->opt_obs > 1 ? h->opt_obs : 1;
+        const size_t need = h->lds_bytes + wave_box_lds_bytes(n_obs, n, h->cfg.N, sizeof(T));
+        if (need > h->geo.max_dyn_lds)
+          return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d with a state box and %d obstacle record%s "
+                      "needs %zu B of LDS per wavefront (> %zu KiB)", h->cfg.N, n_obs,
+                      n_obs > 1 ? "s" : "", need, h->geo.max_dyn_lds / 1024);
+        HIP_TRY(wave_box_iterate<T>(h->cfg, a, h->opt_ls > 1 ? h->opt_ls : 1, n_obs, h->box,
+                                    h->lds_bytes, s));
+        return I2LQR_OK;
+      }
       case K_WAVE_OBS:
         if (h->lds_bytes + wave_obs_lds_bytes(h->opt_obs, sizeof(T)) > h->geo.max_dyn_lds)
           return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d with \"obstacles\" = %d needs %zu B of LDS "
@@ -1604,6 +1628,38 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   return I2LQR_OK;
 }
 
+int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, double q1, double q2) {
+  if (!h) return fail(I2LQR_ERR_INVALID, "null handle");
+  if ((lo == nullptr) != (hi == nullptr))
+    return fail(I2LQR_ERR_INVALID, "state box: lo and hi must both be given or both be NULL");
+  if (!(q1 > 0.0) || !(q2 > 0.0) || std::isinf(q1) || std::isinf(q2))
+    return fail(I2LQR_ERR_INVALID, "state box: q1 and q2 must be positive and finite");
+  i2lqr::StateBox b;
+  b.q1 = q1;
+  b.q2 = q2;
+  for (int i = 0; lo && i < h->cfg.n; i++) {
+    if (std::isnan(lo[i]) || std::isnan(hi[i]))
+      return fail(I2LQR_ERR_INVALID, "state box: bound %d is NaN", i);
+    if (lo[i] >= hi[i])
+      return fail(I2LQR_ERR_INVALID, "state box: lo[%d] = %g is not below hi[%d] = %g", i, lo[i], i,
+                  hi[i]);
+    // an unbounded side keeps its 0: the kernel does no arithmetic on infinities (the masks count)
+    if (!std::isinf(lo[i])) {
+      b.lo[i] = lo[i];
+      b.m_lo |= 1u << i;
+    }
+    if (!std::isinf(hi[i])) {
+      b.hi[i] = hi[i];
+      b.m_hi |= 1u << i;
+    }
+  }
+  if (b.on() && h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR)
+    return fail(I2LQR_ERR_UNSUPPORTED, "a state box is built for the problem-major layout (the "
+                "one-problem-per-wavefront kernel)");
+  h->box = b;
+  return I2LQR_OK;
+}
+
 static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit) {
   if (!h) return "";
   if (h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR) {
@@ -1622,6 +1678,7 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
     case K_GROUP16: return "k_group_iterate (sixteen lanes)";
     case K_GROUP_WS: return "k_group_iterate (workspace form)";
     case K_QUAD: return "k_quad_iterate";
+    case K_WAVE_BOX: return "k_iterate (state box)";
     case K_WAVE_OBS: return "k_iterate (several obstacles)";
     case K_WAVE_LS: return "k_iterate (line search)";
     case K_WAVE: return "k_iterate";
@@ -1657,6 +1714,9 @@ int i2lqr_backward(i2lqr_handle* h, int64_t B, const void* X, const void* U, con
   if (int rc = check_common(h, B)) return rc;
   if (B == 0) return I2LQR_OK;
   if (!X || !U || !x_term || !lamb || !K || !k) return fail(I2LQR_ERR_INVALID, "null buffer");
+  if (h->box.on())
+    return fail(I2LQR_ERR_UNSUPPORTED, "i2lqr_backward has no state box: clear it "
+                "(i2lqr_set_state_box with NULL bounds), or use i2lqr_iterate");
   if (h->opt_obs > 1)
     return fail(I2LQR_ERR_UNSUPPORTED, "i2lqr_backward reads one obstacle record per problem: "
                 "switch \"obstacles\" off, or use i2lqr_iterate");
@@ -1715,6 +1775,10 @@ int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void
   if (!X || !U || !x_term || !lamb || !cost) return fail(I2LQR_ERR_INVALID, "null buffer");
   if ((K == nullptr) != (k == nullptr))
     return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
+  if (h->box.on())
+    return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which has "
+                "no state box: clear it (i2lqr_set_state_box with NULL bounds), or solve the chain "
+                "steps one after the other");
   if (h->opt_obs > 1)
     return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which reads "
                 "one obstacle record per problem: switch \"obstacles\" off, or solve the chain steps "

@@ -508,8 +508,12 @@ template <class T, class Sys, int LANES, bool HASQR, bool FSTEP = false> struct 
   // has no branch, and the return value says whether some Quu was not positive definite — the
   // caller then repeats the pass with GENERAL = true.  Where Quu is positive definite both
   // compute the same numbers (t_quu_inverse2_pd / t_quu_inverse2).
-  template <bool GENERAL = true>
-  __device__ __forceinline__ bool backward(int Xo, int Uo, const T (&xT)[n], T lamb) const {
+  // BOX (k_iterate_box, i2lqr_wave_box.hip): bx holds the state box barrier's d1[N+1][n] (added to
+  // l_x / V_x) and, behind it, d2[N+1][n] (added to the diagonal of l_xx / V_xx), written by
+  // BoxWorker::prep_box.  Without BOX nothing of it is compiled.
+  template <bool GENERAL = true, bool BOX = false>
+  __device__ __forceinline__ bool backward(int Xo, int Uo, const T (&xT)[n], T lamb,
+                                           const T* bx = nullptr) const {
     bool bad = false;
     constexpr int NA = n + 1;                               // width of [Vxx | Vx], [K | k]
     constexpr int P1N = W * NA, P2N = W * W, P4N = n * NA;  // elements per phase
@@ -532,6 +536,10 @@ template <class T, class Sys, int LANES, bool HASQR, bool FSTEP = false> struct 
 #pragma unroll
         for (int r = 0; r < n; r++) v += T(2) * S[L.Qt + i * n + r] * (S[Xo + N * n + r] - xT[r]);
         if (i < 2) v += S[L.ob + N * 5 + i];
+      }
+      if constexpr (BOX) {
+        if (j == i) v += bx[(N + 1) * n + N * n + i];
+        if (j == n) v += bx[N * n + i];
       }
       S[L.Va + e] = v;
     }
@@ -571,6 +579,25 @@ template <class T, class Sys, int LANES, bool HASQR, bool FSTEP = false> struct 
         if (a >= n && b >= n) lc = T(2) * c.R[(a - n) * m + (b - n)];  // l_uu = 2R, :28
       }
       p2_const[r] = lc;
+    }
+    // BOX: d2[t][a] on the diagonal of l_xx (a == b < n), d1[t][a] in l_x (a < n); the other lanes
+    // read word 0
+    [[maybe_unused]] int p2_b[BOX ? P2P : 1], g_b[BOX ? GP : 1];
+    [[maybe_unused]] bool p2_bon[BOX ? P2P : 1], g_bon[BOX ? GP : 1];
+    if constexpr (BOX) {
+#pragma unroll
+      for (int r = 0; r < P2P; r++) {
+        const int e0 = sl + r * LANES;
+        const int e = e0 < P2N ? e0 : 0, a = e / W, b = e - a * W;
+        p2_bon[r] = a == b && a < n;
+        p2_b[r] = p2_bon[r] ? (N + 1) * n + a : 0;
+      }
+#pragma unroll
+      for (int r = 0; r < GP; r++) {
+        const int a = sl + r * LANES;
+        g_bon[r] = a < n;
+        g_b[r] = g_bon[r] ? a : 0;
+      }
     }
     // g[a] = l[a] + T1[a][n]:  l_x obstacle part (a < 2), l_u (a >= n)
     int g_x[GP], g_xs[GP], g_t[GP];
@@ -645,19 +672,28 @@ template <class T, class Sys, int LANES, bool HASQR, bool FSTEP = false> struct 
       // P2: H = L + T1[:, :n] F  ((n+m) x (n+m): Qxx | . ; Qux | Quu),  g = l + T1[:, n].
       // All LDS reads of the phase (H and g operands) are issued before the first store.
       T g_extra[GP], g_t1n[GP];
+      [[maybe_unused]] T g_box[BOX ? GP : 1];
 #pragma unroll
       for (int r = 0; r < GP; r++) {
         g_extra[r] = S[g_x[r] + t * g_xs[r]];
         g_t1n[r] = S[g_t[r]];
+        if constexpr (BOX) g_box[r] = bx[g_b[r] + t * n];
       }
       T h_val[P2P];
 #pragma unroll
       for (int r = 0; r < P2P; r++) {
         const T extra = S[p2_x[r] + t * p2_xs[r]];
+        [[maybe_unused]] T box = T(0);
+        if constexpr (BOX) box = bx[p2_b[r] + t * n];
         T acc = T(0);
 #pragma unroll
         for (int i = 0; i < n; i++) acc = t_fma(S[p2_t[r] + i], S[p2_f[r] + fo + i * W], acc);
-        h_val[r] = (p2_const[r] + (p2_xon[r] ? extra : T(0))) + acc;
+        if constexpr (BOX) {
+          const T lxx = p2_const[r] + (p2_xon[r] ? extra : T(0));
+          h_val[r] = (p2_bon[r] ? lxx + box : lxx) + acc;
+        } else {
+          h_val[r] = (p2_const[r] + (p2_xon[r] ? extra : T(0))) + acc;
+        }
       }
 #pragma unroll
       for (int r = 0; r < P2P; r++)
@@ -674,6 +710,7 @@ template <class T, class Sys, int LANES, bool HASQR, bool FSTEP = false> struct 
               l += T(2) * c.Q[a * n + q] * (S[Xo + t * n + q] - c.xtarget[q]);
           }
         }
+        if constexpr (BOX) l = g_bon[r] ? l + g_box[r] : l;
         if (g_on[r]) S[L.g + sl + r * LANES] = l + g_t1n[r];
       }
       wave_sync();

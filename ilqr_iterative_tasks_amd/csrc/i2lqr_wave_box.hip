@@ -1,0 +1,234 @@
+// k_iterate_box: the one-problem-per-wavefront kernel with a box on the states (speed limits and
+// the like).  NOT the reference's model: its v_min / v_max and tuning_state_q1 / q2
+// (utils/base.py:15-20, 242-302) are read by nothing there.  Opt-in (i2lqr_set_state_box,
+// include/i2lqr.h).
+//
+// For every horizon index t = 0 ... N and every state component i with a finite bound the
+// exponential barrier of add_control_constraint (control/ilqr_helper.py:59-64, 83-103) is applied
+// to x_t[i]:
+//   e_hi = exp(q2 (x - hi)), e_lo = exp(q2 (lo - x))     (0 on a side without bound)
+//   d1 = q1 q2 (e_hi - e_lo) -> l_x[i] (t < N) / V_x[i] (t = N)
+//   d2 = q1 q2^2 (e_hi + e_lo) -> l_xx[i][i] / V_xx[i][i]
+// The barrier enters the derivatives only; the accept / reject cost is the reference's.
+//
+// The (t, i) pairs are independent - each writes its own two words, nothing is summed - so prep_box
+// spreads them over all 64 lanes, not over the lanes that own t as the obstacle records are
+// (DESIGN.md 3.1).  The 2 n (N + 1) words sit in LDS behind the obstacle records, the 2 n bounds
+// behind them.  The backward pass
+// is Worker::backward with BOX = true: three more reads (terminal block, the diagonal of l_xx, l_x),
+// issued with the phase's other reads.  Everything else - records, line search, accept / reject,
+// exit and stores - is k_iterate_obs's (i2lqr_wave_obs.hip), so the box composes with "obstacles"
+// and "line_search".
+#include "i2lqr_wave_box.h"
+
+#include "i2lqr_wave_obs.hpp"  // ObsWorker: LsWorker with the records' prep
+#include "i2lqr_wave_obs.h"    // wave_obs_lds_bytes
+#include "i2lqr_geometry.hpp"
+#include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
+#include "i2lqr_group_launch.hpp"
+
+namespace i2lqr {
+
+template <class T, class Sys, bool HASQR> struct BoxWorker : ObsWorker<T, Sys, HASQR> {
+  using Obs = ObsWorker<T, Sys, HASQR>;
+  using Base = typename Obs::Base;
+  static constexpr int n = Sys::n, m = Sys::m;
+  using Base::N;
+  using Base::S;
+  using Base::sl;
+
+  __device__ BoxWorker(const typename Base::Cfg& c_, T* smem, int lane) : Obs(c_, smem, lane) {}
+
+  // once per kernel: the bounds into LDS behind d1, d2 (lo[n], hi[n]).  A lane-dependent index
+  // into the by-value argument compiles to a vector load from the kernel-argument segment - host
+  // memory, several microseconds - in every prep_box; here every lane stores the uniform values.
+  __device__ __forceinline__ void stage_box(const BoxCfg<T, n>& b, T* bx) const {
+    T* bl = bx + 2 * (N + 1) * n;
+#pragma unroll
+    for (int i = 0; i < n; i++) {
+      bl[i] = b.lo[i];
+      bl[n + i] = b.hi[i];
+    }
+  }
+
+  // d1, d2 of every (t, i), t = 0 ... N (index N is the terminal term): pair p = t n + i is word p
+  // of the trajectory and of each of the two arrays behind bx.  An unbounded side is masked out (its
+  // bound is stored as 0: the exponential of a finite number, dropped by the select).  No
+  // wave_sync: the caller's prep_obs ends with one.
+  __device__ __forceinline__ void prep_box(int Xo, const BoxCfg<T, n>& b, T* bx) const {
+    const int P = (N + 1) * n;
+    const T* bl = bx + 2 * P;
+    for (int p = sl; p < P; p += 64) {
+      const int i = p % n;
+      const T x = S[Xo + p];
+      const T e_hi = t_exp(b.q2 * (x - bl[n + i]));
+      const T e_lo = t_exp(b.q2 * (bl[i] - x));
+      const T eh = ((b.m_hi >> i) & 1u) ? e_hi : T(0);
+      const T el = ((b.m_lo >> i) & 1u) ? e_lo : T(0);
+      bx[p] = b.q12 * (eh - el);
+      bx[P + p] = b.q122 * (eh + el);
+    }
+  }
+};
+
+// k_iterate_obs (i2lqr_wave_obs.hip) with prep_box in front of prep_obs and the BOX backward pass.
+template <class T, class Sys, bool HASQR>
+__global__ __launch_bounds__(64) void k_iterate_box(const DevCfg<T, Sys::n, Sys::m> c,
+                                                    const IterArgs<T> a, const int steps,
+                                                    const int n_obs, const BoxCfg<T, Sys::n> box) {
+  constexpr int n = Sys::n, m = Sys::m;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int lane = threadIdx.x;
+  const int64_t prob = blockIdx.x;
+  if (prob >= a.B) return;
+  BoxWorker<T, Sys, HASQR> w(c, reinterpret_cast<T*>(smem_raw), lane);
+  const int N = c.N;
+  const auto& L = w.L;
+  const auto S = w.S;
+  const int K = n_obs < 1 ? 1 : (n_obs > I2LQR_MAX_OBSTACLES ? I2LQR_MAX_OBSTACLES : n_obs);
+
+  // entry: x0, U, x_term, lamb, record 0  (HBM -> LDS/registers), as k_iterate
+  T xT[n], ob[6];
+  const T* gX = a.X + prob * (int64_t)(n * (N + 1));
+  if (w.sl < n) S[L.X0 + w.sl] = gX[w.sl * (N + 1)];
+  w.load_rec(a.U + prob * (int64_t)(m * N), L.U0, m, N);
+#pragma unroll
+  for (int i = 0; i < n; i++) xT[i] = a.x_term[prob * n + i];
+  const T* gob = a.obs ? a.obs + prob * (int64_t)(K * 6) : nullptr;  // this problem's obs[K][6]
+#pragma unroll
+  for (int q = 0; q < 6; q++) ob[q] = gob ? gob[q] : T(q == 5 ? -1 : 1);
+  // ... and all K records behind the slice (wave_obs_lds_bytes; visible after the wave_sync below)
+  static_assert(I2LQR_MAX_OBSTACLES * 6 <= 64, "one record word per lane");
+  T* recs = reinterpret_cast<T*>(smem_raw) + L.total;
+  if (gob && lane < K * 6) recs[lane] = gob[lane];
+  T* bx = recs + K * 6;  // d1[N+1][n], d2[N+1][n], lo[n], hi[n] behind the records (wave_box_lds_bytes)
+  w.stage_box(box, bx);
+  w.stage_consts();
+  T lamb = a.lamb[prob];
+  // this lane's candidate: j = lane mod steps, alpha = 2^-j
+  const int A = steps < 1 ? 1 : (steps > kLsMaxSteps ? kLsMaxSteps : steps);
+  const T alpha_lane = T(1) / T(1 << (lane % A));
+  wave_sync();
+
+  int cur = 0;  // which of the two trajectory buffers holds the nominal
+  T cost = w.rollout(L.X0, L.U0, xT);
+  int it = 0, status = a.early_exit ? 2 /*MAX_ITER*/ : 0 /*RUNNING*/;
+  T cost_ret = cost;
+  bool fresh = true;  // the nominal trajectory changed since the last prep
+  while (it < a.n_iters) {
+    const int Xo = cur ? L.X1 : L.X0, Uo = cur ? L.U1 : L.U0;
+    const int Xn = cur ? L.X0 : L.X1, Un = cur ? L.U0 : L.U1;
+    if (fresh) {
+      w.prep_box(Xo, box, bx);  // (made visible by the wave_sync that ends prep_obs)
+      w.prep_obs(Xo, Uo, ob, gob ? recs : nullptr, K);
+    }
+    if (__builtin_expect(__any(w.template backward<false, true>(Xo, Uo, xT, lamb, bx)), 0))
+      w.template backward<true, true>(Xo, Uo, xT, lamb, bx);
+    // the candidates: optimistic sincos first, the general form for ALL of them if one candidate
+    // left the short kernel's range (lane by lane the two forms agree bit for bit inside it)
+    bool big = false;
+    T cost_lane = w.template forward_ls<false>(Xo, Uo, Xn, Un, xT, alpha_lane, &big);
+    const bool general = __any(big);
+    if (__builtin_expect(general, 0))
+      cost_lane = w.template forward_ls<true>(Xo, Uo, Xn, Un, xT, alpha_lane, &big);
+    // j* = argmin_j cost_j: lane j holds candidate j; NaN never wins, ties go to the smallest j
+    int js = 0;
+    T best = (T)INFINITY;
+#pragma unroll
+    for (int j = 0; j < kLsMaxSteps; j++) {
+      const T cj = __shfl(cost_lane, j);
+      if (j < A && cj < best) {
+        best = cj;
+        js = j;
+      }
+    }
+    const T cost_new = __shfl(cost_lane, js);
+    it++;
+    // accept / reject with the lamb schedule: control/iterative_ilqr.py:74-84
+    fresh = cost_new < cost;
+    if (fresh) {
+      if (js != 0) {  // (Xn, Un) hold the full step's trajectory: roll the winner out on every lane
+        const T alpha = T(1) / T(1 << js);
+        if (general) w.template forward_ls<true>(Xo, Uo, Xn, Un, xT, alpha, &big);
+        else w.template forward_ls<false>(Xo, Uo, Xn, Un, xT, alpha, &big);
+      }
+      cur ^= 1;
+      lamb /= c.lamb_factor;
+      const bool conv = t_abs((cost_new - cost) / cost) < c.eps;
+      cost_ret = cost_new;
+      // next nominal cost: stage terms are measured to xtarget, not x_terminal, when Q != 0
+      cost = HASQR ? w.nominal_cost(Xn, Un, xT) : cost_new;
+      if (conv) {
+        if (a.early_exit) { status = 1; break; }
+        if (status == 0) status = 1;
+      }
+    } else {
+      lamb *= c.lamb_factor;
+      cost_ret = cost;
+      if (lamb > c.max_lamb) {
+        if (a.early_exit) { status = 3; break; }
+        if (status == 0) status = 3;
+      }
+    }
+  }
+  if (!t_isfinite(cost_ret)) status = 4;
+
+  // exit: X, U, gains (the backward pass's, unscaled), scalars (LDS -> HBM)
+  const int Xo = cur ? L.X1 : L.X0, Uo = cur ? L.U1 : L.U0;
+  w.store_rec(a.X + prob * (int64_t)(n * (N + 1)), Xo, n, N + 1);
+  w.store_rec(a.U + prob * (int64_t)(m * N), Uo, m, N);
+  if (a.K) w.store_gains(a.K + prob * (int64_t)(m * n * N), a.k + prob * (int64_t)(m * N));
+  if (w.sl == 0) {
+    a.lamb[prob] = lamb;
+    a.cost[prob] = cost_ret;
+    if (a.iters) a.iters[prob] = it;
+    if (a.status) a.status[prob] = status;
+  }
+}
+
+I2LQR_WAVE_BOX_KERNELS(template __global__, double)
+I2LQR_WAVE_BOX_KERNELS(template __global__, float)
+
+namespace {
+
+template <class T, class Sys, bool HASQR>
+hipError_t launch_box(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, int n_obs,
+                      const StateBox& box, size_t lds, hipStream_t s) {
+  constexpr int n = Sys::n;
+  const auto c = make_dev_cfg<T, Sys::n, Sys::m>(cfg);
+  BoxCfg<T, n> b;
+  for (int i = 0; i < n; i++) {
+    b.lo[i] = (T)box.lo[i];
+    b.hi[i] = (T)box.hi[i];
+  }
+  const T q1 = (T)box.q1;
+  b.q2 = (T)box.q2;
+  b.q12 = q1 * b.q2;  // (as make_dev_cfg forms ctrl_q12 / ctrl_q122)
+  b.q122 = q1 * (b.q2 * b.q2);
+  b.m_lo = box.m_lo & ((1u << n) - 1);
+  b.m_hi = box.m_hi & ((1u << n) - 1);
+  lds += wave_box_lds_bytes(n_obs, n, cfg.N, sizeof(T));  // records, d1, d2 behind the slice
+  if (hipError_t e = raise_lds_limit<k_iterate_box<T, Sys, HASQR>>(lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL((k_iterate_box<T, Sys, HASQR>), dim3((unsigned)a.B), dim3(64), lds, s, c, a,
+                     steps, n_obs, b);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+template <class T>
+hipError_t wave_box_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, int n_obs,
+                            const StateBox& box, size_t lds, hipStream_t s) {
+  return visit_plant<T>(cfg, [&](auto, auto sys) {
+    using Sys = decltype(sys);
+    return has_stage_weights(cfg) ? launch_box<T, Sys, true>(cfg, a, steps, n_obs, box, lds, s)
+                                  : launch_box<T, Sys, false>(cfg, a, steps, n_obs, box, lds, s);
+  });
+}
+
+template hipError_t wave_box_iterate<double>(const i2lqr_config&, const IterArgs<double>&, int, int,
+                                             const StateBox&, size_t, hipStream_t);
+template hipError_t wave_box_iterate<float>(const i2lqr_config&, const IterArgs<float>&, int, int,
+                                            const StateBox&, size_t, hipStream_t);
+
+}  // namespace i2lqr

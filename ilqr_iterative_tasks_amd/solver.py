@@ -48,6 +48,7 @@ class BatchedILQR:
         self.batch_tiled = cfg.layout == _abi.LAYOUT_BATCH_TILED
         self._ws = None  # scratch of the batch-minor kernels (registered on the handle)
         self.obstacles = 1  # obstacle records per problem ("obstacles" option: 2 ... 8)
+        self.state_box = None  # (lo, hi, q1, q2) of set_state_box() while some bound is finite
 
     # -- plumbing ---------------------------------------------------------------------------
     def _check(self, rc: int) -> None:
@@ -160,6 +161,30 @@ class BatchedILQR:
         self._check(self.lib.i2lqr_set_option(self._handle, name.encode(), int(value)))
         if name == "obstacles":
             self.obstacles = int(value) if int(value) > 1 else 1
+
+    def set_state_box(self, lo=None, hi=None, q1: float = 1.0, q2: float = 1.0) -> None:
+        """A box on the states (i2lqr_set_state_box in include/i2lqr.h; not the reference's model):
+        lo[n], hi[n] with -inf / +inf (or None for the whole side) where there is no bound.  For
+        every x_t[i] with a finite bound the exponential barrier q1 exp(q2 (x - hi)) +
+        q1 exp(q2 (lo - x)) enters the backward pass's derivatives (not the accept / reject cost: the
+        bound is soft).  While a bound is finite every call runs on k_iterate_box, which composes
+        with "obstacles" and "line_search"; set_state_box() with no finite bound switches it off
+        (today's kernels, bit for bit).  `state_box` holds (lo, hi, q1, q2) while it is on."""
+        import numpy as np
+        if lo is None and hi is None:
+            self._check(self.lib.i2lqr_set_state_box(self._handle, None, None, float(q1), float(q2)))
+            self.state_box = None
+            return
+        lo_a = np.full(self.n, -np.inf) if lo is None else np.array(lo, dtype=np.float64).ravel()
+        hi_a = np.full(self.n, np.inf) if hi is None else np.array(hi, dtype=np.float64).ravel()
+        if lo_a.shape != (self.n,) or hi_a.shape != (self.n,):
+            raise ValueError(f"state box: lo and hi hold n = {self.n} values each, got "
+                             f"{lo_a.shape} and {hi_a.shape}")
+        arr = lambda a: (C.c_double * self.n)(*a.tolist())
+        self._check(self.lib.i2lqr_set_state_box(self._handle, arr(lo_a), arr(hi_a), float(q1),
+                                                 float(q2)))
+        finite = bool(np.isfinite(lo_a).any() or np.isfinite(hi_a).any())
+        self.state_box = (lo_a, hi_a, float(q1), float(q2)) if finite else None
 
     def iterate_kernel(self, B: int) -> str:
         """Name of the kernel iterate() launches for B problems (rocprofv3 traces)."""

@@ -388,8 +388,31 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  */
 int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value);
 
+/* A box on the states (speed limits and the like) - NOT the reference's model: its v_min / v_max
+ * and tuning_state_q1 / tuning_state_q2 (utils/base.py:15-20, 242-302) are read by nothing there.
+ * Off by default.  lo, hi: HOST pointers to n doubles each; -INFINITY / +INFINITY = no bound on that
+ * side; both NULL, or nothing finite: off (today's kernels, bit for bit).  For every horizon index
+ * t = 0 ... N and every state component i with a finite bound the exponential barrier of
+ * add_control_constraint / repelling_cost_function (control/ilqr_helper.py:59-64, 83-103) is
+ * applied to the state:
+ *   e_hi = exp(q2 (x_t[i] - hi[i]))      (0 if hi[i] = +inf)
+ *   e_lo = exp(q2 (lo[i] - x_t[i]))      (0 if lo[i] = -inf)
+ *   d1[t][i] = q1 q2   (e_hi - e_lo)  -> added to l_x[i]     (t < N) / V_x[i]     (t = N)
+ *   d2[t][i] = q1 q2^2 (e_hi + e_lo)  -> added to l_xx[i][i] (t < N) / V_xx[i][i] (t = N)
+ * Stage terms use x_t, as the obstacle barrier does; the terminal term uses x_N.  The barrier enters
+ * the derivatives only: the accept / reject cost stays the reference's
+ * (control/iterative_ilqr.py:43-48), as for the input and obstacle barriers, so the bound is soft.
+ * Rollouts, forward pass, line search, lamb schedule, status words and stored gains are unchanged.
+ * While a bound is finite EVERY call of the handle, whatever the batch size, runs on k_iterate_box -
+ * one problem per wavefront (three plants, both precisions, with or without stage weights); it
+ * composes with "obstacles" and "line_search".  i2lqr_backward, i2lqr_solve_chained and a forced
+ * "group_lanes" 8 or 16 answer I2LQR_ERR_UNSUPPORTED; i2lqr_iterate_pick takes its unfused form.
+ * I2LQR_ERR_INVALID: a NaN bound, lo[i] >= hi[i], q1 <= 0 or q2 <= 0, exactly one pointer NULL.
+ * I2LQR_ERR_UNSUPPORTED: a finite bound on a batch-minor / batch-tiled handle. */
+int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, double q1, double q2);
+
 /* Name of the kernel i2lqr_iterate (fixed iteration count) launches for a batch of B problems
- * with the handle's current options: "k_iterate", "k_iterate (line search)", "k_iterate (several obstacles)", "k_group_iterate", "k_group_iterate (sixteen
+ * with the handle's current options: "k_iterate", "k_iterate (line search)", "k_iterate (several obstacles)", "k_iterate (state box)", "k_group_iterate", "k_group_iterate (sixteen
  * lanes)", "k_group_iterate (workspace form)", "k_group_spec", "k_group_spec (sixteen lanes)",
  * "k_quad_iterate", "k_lane_iterate", "k_lane_iterate_pair" (the helper-wavefront form),
  * "k_lane_iterate_rows"; "unsupported" if a forced option cannot be honoured and the launch would
