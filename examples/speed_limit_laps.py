@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--num-ss-points", type=int, default=8)
     ap.add_argument("--num-ss-iters", type=int, default=2)
     ap.add_argument("--lamb-mode", default="chained", choices=["chained", "independent"])
+    ap.add_argument("--wave-chain", action="store_true",
+                    help="chained laps in one launch per round (the \"wave_chain\" option: k_chain_box)")
     args = ap.parse_args()
 
     dt = 1
@@ -48,7 +50,8 @@ def main():
                       num_horizon=6, tuning_state_q1=args.q1, tuning_state_q2=args.q2)
     box = None if args.no_limit else state_box_from_params(system, param)
     ctrl = iLqr(param, obstacle=Obstacle(31, -3, 8, 6), system_param=system,
-                solver=HipCandidateSolver(state_box=box), lamb_mode=args.lamb_mode)
+                solver=HipCandidateSolver(state_box=box, wave_chain=args.wave_chain),
+                lamb_mode=args.lamb_mode)
     ctrl.add_trajectory(ego.xcl, ego.ucl)
     ctrl.set_timestep(dt)
     ego.set_ctrl_policy(ctrl)

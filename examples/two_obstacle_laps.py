@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--num-ss-points", type=int, default=8)
     ap.add_argument("--num-ss-iters", type=int, default=2)
     ap.add_argument("--lamb-mode", default="chained", choices=["chained", "independent"])
+    ap.add_argument("--wave-chain", action="store_true",
+                    help="chained laps in one launch per round (the \"wave_chain\" option: k_chain_box)")
     args = ap.parse_args()
 
     dt = 1
@@ -44,7 +46,7 @@ def main():
     moving = dict(spd=args.moving_up, timestep=dt, moving_option=1) if args.moving_up else {}
     obstacles = ObstacleSet([Obstacle(31, -3, 8, 6), Obstacle(*args.second, **moving)])
     ctrl = iLqr(param, obstacle=obstacles, system_param=KineticBicycleParam(),
-                solver=HipCandidateSolver(), lamb_mode=args.lamb_mode)
+                solver=HipCandidateSolver(wave_chain=args.wave_chain), lamb_mode=args.lamb_mode)
     ctrl.add_trajectory(ego.xcl, ego.ucl)
     ctrl.set_timestep(dt)
     ego.set_ctrl_policy(ctrl)

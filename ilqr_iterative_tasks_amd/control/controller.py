@@ -85,7 +85,9 @@ class iLqr(ControlBase):
         # device_rounds: run the three outer rounds (select / solve / relaxed cost / pick) on the
         # GPU with one read-back per control step (control/device_round.py; independent lamb)
         assert not device_rounds or lamb_mode == "independent"
-        if getattr(solver, "line_search", 1) > 1 and (lamb_mode == "chained" or device_rounds):
+        # (a solver with wave_chain runs chained laps with a line search: k_chain_box)
+        if getattr(solver, "line_search", 1) > 1 and (
+                (lamb_mode == "chained" and not getattr(solver, "wave_chain", False)) or device_rounds):
             raise ValueError("a solver with line_search > 1 is for lamb_mode=\"independent\" without "
                              "device_rounds: the chain kernel and the device rounds have no line search")
         if getattr(solver, "state_box", None) is not None and device_rounds:

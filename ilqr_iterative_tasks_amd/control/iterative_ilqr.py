@@ -22,7 +22,7 @@ class HipCandidateSolver:
     line_search = 2, 4 or 8: every handle is created problem-major, whatever layout the library
     recommends for the batch, with the "line_search" option set (include/i2lqr.h: that many step
     sizes 2^-j per iteration on k_iterate_ls — not the reference's algorithm); independent lamb
-    only, solve_chained raises.
+    only, solve_chained raises unless wave_chain is on.
 
     An obstacle record of shape (K, 6) with K > 1 (params.obstacle_record of an ObstacleSet) is K
     obstacles per problem — not the reference's model: solve() and solve_chained() (a launch per
@@ -32,15 +32,22 @@ class HipCandidateSolver:
     state_box = a params.StateBox with a finite bound (not the reference's model either): every
     handle is created problem-major and gets the box (i2lqr_set_state_box, k_iterate_box);
     solve() and solve_chained() (a launch per chain step) work, candidate_round / sharded_round
-    raise."""
+    raise.
 
-    def __init__(self, device="cuda:0", dtype="f64", line_search=1, state_box=None):
+    wave_chain = True: every problem-major handle gets the "wave_chain" option, so solve_chained
+    runs laps of equal length in ONE launch (k_chain_box, one wavefront per lap) with line_search,
+    several obstacles, a state box, stage weights or quad12 as well; ragged laps keep the launch
+    per chain step."""
+
+    def __init__(self, device="cuda:0", dtype="f64", line_search=1, state_box=None,
+                 wave_chain=False):
         if int(line_search) not in (-1, 0, 1, 2, 4, 8):
             raise ValueError(f"line_search is 2, 4 or 8 step sizes, or -1 / 0 / 1 (off): got {line_search}")
         self.device = device
         self.dtype = dtype
         self.line_search = int(line_search) if int(line_search) > 1 else 1
         self.state_box = state_box if state_box is not None and state_box.active else None
+        self.wave_chain = bool(wave_chain)
         self._solvers = {}
 
     @staticmethod
@@ -86,6 +93,8 @@ class HipCandidateSolver:
             key += self.state_box.key()
         if key not in self._solvers:
             self._solvers[key] = BatchedILQR(cfg, self.device)
+            if self.wave_chain and cfg.layout == 0:
+                self._solvers[key].set_option("wave_chain", 1)
             if self.line_search > 1:
                 self._solvers[key].set_option("line_search", self.line_search)
             if n_obs > 1:
@@ -393,12 +402,14 @@ class HipCandidateSolver:
         (ragged laps; configurations the chain kernel is not built for): step c of every chain is
         one launch (i2lqr_solve over the chains that still have a candidate c), its lamb input
         gathered on the device from step c - 1's output, the launches replayed as a hipGraph.
+        With wave_chain=True the one launch also covers what the speculative kernel is not built
+        for (k_chain_box: line_search, several obstacles, a state box, stage weights, quad12).
         Either way ONE synchronisation per round — against a host round trip per step (the
         controller's loop before: 24 per control step on BASELINE configs[0]).  Same kernel code on
         the same inputs: bit-identical to the step-by-step form.
         Returns one dict(U, X, lamb, cost, iters, status) per chain (host arrays, leading axis k_a)."""
         import torch
-        if self.line_search > 1:
+        if self.line_search > 1 and not self.wave_chain:
             raise ValueError("solve_chained: line_search is built for independent lamb (the chain "
                              "kernel has no line search)")
         chains = [np.atleast_2d(np.asarray(xt, float)) for xt in x_terms_by_chain]

@@ -24,6 +24,7 @@
 #include "i2lqr_select.hpp"
 #include "i2lqr_wave_ls.h"
 #include "i2lqr_wave_box.h"
+#include "i2lqr_wave_chain.h"
 #include "i2lqr_wave_obs.h"
 
 #define I2LQR_DRY_RUN_LANE 1
@@ -172,6 +173,7 @@ struct i2lqr_handle {
   int opt_group_overlap = -1;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; -1 = automatic (on)
   int opt_obs = 0;  // one-problem-per-wavefront kernel: obstacle records per problem (k_iterate_obs): 2 ... I2LQR_MAX_OBSTACLES; 0: off (one record)
   i2lqr::StateBox box;  // one-problem-per-wavefront kernel: the state box (k_iterate_box, i2lqr_set_state_box); box.on(): some bound is finite
+  int opt_wave_chain = 0;  // i2lqr_solve_chained: 1 = what the speculative chain kernel is not built for runs on the one-problem-per-wavefront kernel's chained form (k_chain_box); 0: refused
   int opt_ls = 0;  // one-problem-per-wavefront kernel: step sizes of the parallel line search (k_iterate_ls): 2, 4, 8; 0: off
   int opt_group_fixed = -1;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; -1 = automatic (on)
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
@@ -506,13 +508,44 @@ template <class T, class Sys> struct Launch {
     return I2LQR_OK;
   }
   static int names_pair(i2lqr_handle*, int64_t, int) { return 0; }
-  // L chains of k problems each in ONE launch (k_group_spec<.., CHAIN>)
+  // "wave_chain" 1: L chains of k problems each in one launch of k_chain_box (i2lqr_wave_chain.hip),
+  // with the handle's state box, "obstacles" and "line_search"
+  static int wave_chain(i2lqr_handle* h, int64_t L, int k, void* X, void* U, const void* x_term,
+                        void* lamb, const void* obs, void* cost, void* K, void* kk, int32_t* iters,
+                        int32_t* status, hipStream_t s) {
+    const bool model = h->box.on() || h->opt_obs > 1 || h->opt_ls > 1;
+    if (model && (h->opt_group == 8 || h->opt_group == 16)) {  // (as i2lqr_solve refuses them)
+      const char* why = "";
+      (void)select_fused(h, L, true, &why);
+      return fail(I2LQR_ERR_UNSUPPORTED, "%s", why);
+    }
+    const int n_obs = h->opt_obs > 1 ? h->opt_obs : 1;
+    const size_t need = h->lds_bytes + wave_box_lds_bytes(n_obs, n, h->cfg.N, sizeof(T));
+    if (need > h->geo.max_dyn_lds)
+      return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d with \"wave_chain\" and %d obstacle record%s "
+                  "needs %zu B of LDS per wavefront (> %zu KiB)", h->cfg.N, n_obs,
+                  n_obs > 1 ? "s" : "", need, h->geo.max_dyn_lds / 1024);
+    IterArgs<T> a = iter_args<T>(L, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, kk, iters,
+                                 status);
+    a.chain_len = k;
+    HIP_TRY(wave_chain_solve<T>(h->cfg, a, h->opt_ls > 1 ? h->opt_ls : 1, n_obs, h->box,
+                                h->lds_bytes, s));
+    return I2LQR_OK;
+  }
+  // L chains of k problems each in ONE launch (k_group_spec<.., CHAIN>; "wave_chain" 1: k_chain_box
+  // where that kernel is not built for the handle)
   static int solve_chained(i2lqr_handle* h, int64_t L, int k, void* X, void* U, const void* x_term,
                            void* lamb, const void* obs, void* cost, void* K, void* kk, int32_t* iters,
                            int32_t* status, hipStream_t s) {
+    const bool wc = h->opt_wave_chain == 1;
+    if (wc && (h->box.on() || h->opt_obs > 1 || h->opt_ls > 1))
+      return wave_chain(h, L, k, X, U, x_term, lamb, obs, cost, K, kk, iters, status, s);
     if constexpr (m == 2 && n + m <= 8) {
-      if (h->opt_spec == 0 || h->opt_group == 8 || h->opt_group == 64 ||
-          !group_spec_chain_supported(h->cfg, L))
+      const bool spec = !(h->opt_spec == 0 || h->opt_group == 8 || h->opt_group == 64 ||
+                          !group_spec_chain_supported(h->cfg, L));
+      if (!spec && wc)
+        return wave_chain(h, L, k, X, U, x_term, lamb, obs, cost, K, kk, iters, status, s);
+      if (!spec)
         return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel: a "
                     "bicycle plant with Q = R = 0, at most %lld chains, a horizon whose three-wavefront "
                     "buffers fit a CU's LDS (solve the chain steps one after the other instead)",
@@ -523,6 +556,7 @@ template <class T, class Sys> struct Launch {
       HIP_TRY(group_spec_chain<T>(h->cfg, a, s));
       return I2LQR_OK;
     }
+    if (wc) return wave_chain(h, L, k, X, U, x_term, lamb, obs, cost, K, kk, iters, status, s);
     return fail(I2LQR_ERR_UNSUPPORTED, "chains are built for the m = 2 plants");
   }
   static int rollout(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term, void* cost,
@@ -1619,6 +1653,14 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
                   "one-problem-per-wavefront kernel)");
     h->opt_obs = v > 1 ? v : 0;
   }
+  else if (!strcmp(name, "wave_chain")) {
+    if (v != -1 && v != 0 && v != 1)
+      return fail(I2LQR_ERR_INVALID, "\"wave_chain\" is 1 (on), or -1 / 0 (off)");
+    if (v == 1 && h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR)
+      return fail(I2LQR_ERR_UNSUPPORTED, "\"wave_chain\" is built for the problem-major layout (the "
+                  "one-problem-per-wavefront kernel)");
+    h->opt_wave_chain = v == 1 ? 1 : 0;
+  }
   else if (!strcmp(name, "group_lanes")) {
     if (v != -1 && v != 8 && v != 16 && v != 64)
       return fail(I2LQR_ERR_INVALID, "\"group_lanes\" is 8, 16, 64 or -1");
@@ -1775,15 +1817,16 @@ int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void
   if (!X || !U || !x_term || !lamb || !cost) return fail(I2LQR_ERR_INVALID, "null buffer");
   if ((K == nullptr) != (k == nullptr))
     return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
-  if (h->box.on())
+  const bool wc = h->opt_wave_chain == 1;  // (k_chain_box carries the three models refused below)
+  if (!wc && h->box.on())
     return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which has "
                 "no state box: clear it (i2lqr_set_state_box with NULL bounds), or solve the chain "
                 "steps one after the other");
-  if (h->opt_obs > 1)
+  if (!wc && h->opt_obs > 1)
     return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which reads "
                 "one obstacle record per problem: switch \"obstacles\" off, or solve the chain steps "
                 "one after the other");
-  if (h->opt_ls > 1)
+  if (!wc && h->opt_ls > 1)
     return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which has "
                 "no line search: switch \"line_search\" off, or solve the chain steps one after the "
                 "other");

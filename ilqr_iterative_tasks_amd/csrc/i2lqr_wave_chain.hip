@@ -1,0 +1,189 @@
+// k_chain_box: a chain of dependent solves in one launch on the one-problem-per-wavefront family.
+// In the controller's "chained" mode (utils/base.py:393, :414-426) the final lamb of candidate c of
+// a lap seeds candidate c + 1; the sixteen-lane speculative kernel runs such chains for the plain
+// bicycles only (k_group_spec<.., CHAIN>, i2lqr_group.hip).  Here one wavefront runs k_iterate_box's
+// solve (i2lqr_wave_box.hip) chain_len times, lamb carried in a register: every model of that
+// kernel - state box, several obstacles, line search, stage weights, quad12 - and with the box
+// off, one record and one step size the numbers of k_iterate.  Opt-in ("wave_chain",
+// include/i2lqr.h).
+//
+// The per-problem body is k_iterate_box's, line for line, and stands here a second time: calling
+// one shared function from both kernels changed k_iterate_box's generated code.
+// What differs: the problem index, the lamb load (first problem of the chain only), and the
+// wave_sync() that ends a problem - its exit stores read the trajectory and the gains from the LDS
+// that the next problem's entry overwrites.
+#include "i2lqr_wave_chain.h"
+
+#include "i2lqr_wave_box.hpp"  // BoxWorker: ObsWorker with the box's prep
+#include "i2lqr_geometry.hpp"
+#include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
+#include "i2lqr_group_launch.hpp"
+
+namespace i2lqr {
+
+template <class T, class Sys, bool HASQR>
+__global__ __launch_bounds__(64) void k_chain_box(const DevCfg<T, Sys::n, Sys::m> c,
+                                                  const IterArgs<T> a, const int steps,
+                                                  const int n_obs, const BoxCfg<T, Sys::n> box) {
+  constexpr int n = Sys::n, m = Sys::m;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int lane = threadIdx.x;
+  const int64_t chain = blockIdx.x;
+  if (chain >= a.B) return;  // (the only exit: chain_len is uniform, every lane runs every problem)
+  BoxWorker<T, Sys, HASQR> w(c, reinterpret_cast<T*>(smem_raw), lane);
+  const int N = c.N;
+  const auto& L = w.L;
+  const auto S = w.S;
+  const int K = n_obs < 1 ? 1 : (n_obs > I2LQR_MAX_OBSTACLES ? I2LQR_MAX_OBSTACLES : n_obs);
+  static_assert(I2LQR_MAX_OBSTACLES * 6 <= 64, "one record word per lane");
+  T* recs = reinterpret_cast<T*>(smem_raw) + L.total;  // obs[K][6] behind the slice
+  T* bx = recs + K * 6;  // d1[N+1][n], d2[N+1][n], lo[n], hi[n] behind the records (wave_box_lds_bytes)
+  // once per kernel, the same for every problem of the chain: the bounds, Q_terminal
+  w.stage_box(box, bx);
+  w.stage_consts();
+  // this lane's candidate: j = lane mod steps, alpha = 2^-j
+  const int A = steps < 1 ? 1 : (steps > kLsMaxSteps ? kLsMaxSteps : steps);
+  const T alpha_lane = T(1) / T(1 << (lane % A));
+  const int clen = a.chain_len;
+  T lamb = a.lamb[chain * clen];  // of the chain's first problem; the later ones take the carry
+
+  for (int ci = 0; ci < clen; ci++) {
+    const int64_t prob = chain * clen + ci;
+    // entry: x0, U, x_term, the records  (HBM -> LDS/registers), as k_iterate_box
+    T xT[n], ob[6];
+    const T* gX = a.X + prob * (int64_t)(n * (N + 1));
+    if (w.sl < n) S[L.X0 + w.sl] = gX[w.sl * (N + 1)];
+    w.load_rec(a.U + prob * (int64_t)(m * N), L.U0, m, N);
+#pragma unroll
+    for (int i = 0; i < n; i++) xT[i] = a.x_term[prob * n + i];
+    const T* gob = a.obs ? a.obs + prob * (int64_t)(K * 6) : nullptr;  // this problem's obs[K][6]
+#pragma unroll
+    for (int q = 0; q < 6; q++) ob[q] = gob ? gob[q] : T(q == 5 ? -1 : 1);
+    if (gob && lane < K * 6) recs[lane] = gob[lane];
+    wave_sync();
+
+    // per problem: all of the solve's state but lamb
+    int cur = 0;  // which of the two trajectory buffers holds the nominal
+    T cost = w.rollout(L.X0, L.U0, xT);
+    int it = 0, status = a.early_exit ? 2 /*MAX_ITER*/ : 0 /*RUNNING*/;
+    T cost_ret = cost;
+    bool fresh = true;  // the nominal trajectory changed since the last prep
+    while (it < a.n_iters) {
+      const int Xo = cur ? L.X1 : L.X0, Uo = cur ? L.U1 : L.U0;
+      const int Xn = cur ? L.X0 : L.X1, Un = cur ? L.U0 : L.U1;
+      if (fresh) {
+        w.prep_box(Xo, box, bx);  // (made visible by the wave_sync that ends prep_obs)
+        w.prep_obs(Xo, Uo, ob, gob ? recs : nullptr, K);
+      }
+      if (__builtin_expect(__any(w.template backward<false, true>(Xo, Uo, xT, lamb, bx)), 0))
+        w.template backward<true, true>(Xo, Uo, xT, lamb, bx);
+      // the candidates: optimistic sincos first, the general form for ALL of them if one candidate
+      // left the short kernel's range (lane by lane the two forms agree bit for bit inside it)
+      bool big = false;
+      T cost_lane = w.template forward_ls<false>(Xo, Uo, Xn, Un, xT, alpha_lane, &big);
+      const bool general = __any(big);
+      if (__builtin_expect(general, 0))
+        cost_lane = w.template forward_ls<true>(Xo, Uo, Xn, Un, xT, alpha_lane, &big);
+      // j* = argmin_j cost_j: lane j holds candidate j; NaN never wins, ties go to the smallest j
+      int js = 0;
+      T best = (T)INFINITY;
+#pragma unroll
+      for (int j = 0; j < kLsMaxSteps; j++) {
+        const T cj = __shfl(cost_lane, j);
+        if (j < A && cj < best) {
+          best = cj;
+          js = j;
+        }
+      }
+      const T cost_new = __shfl(cost_lane, js);
+      it++;
+      // accept / reject with the lamb schedule: control/iterative_ilqr.py:74-84
+      fresh = cost_new < cost;
+      if (fresh) {
+        if (js != 0) {  // (Xn, Un) hold the full step's trajectory: roll the winner out on every lane
+          const T alpha = T(1) / T(1 << js);
+          if (general) w.template forward_ls<true>(Xo, Uo, Xn, Un, xT, alpha, &big);
+          else w.template forward_ls<false>(Xo, Uo, Xn, Un, xT, alpha, &big);
+        }
+        cur ^= 1;
+        lamb /= c.lamb_factor;
+        const bool conv = t_abs((cost_new - cost) / cost) < c.eps;
+        cost_ret = cost_new;
+        // next nominal cost: stage terms are measured to xtarget, not x_terminal, when Q != 0
+        cost = HASQR ? w.nominal_cost(Xn, Un, xT) : cost_new;
+        if (conv) {
+          if (a.early_exit) { status = 1; break; }
+          if (status == 0) status = 1;
+        }
+      } else {
+        lamb *= c.lamb_factor;
+        cost_ret = cost;
+        if (lamb > c.max_lamb) {
+          if (a.early_exit) { status = 3; break; }
+          if (status == 0) status = 3;
+        }
+      }
+    }
+    if (!t_isfinite(cost_ret)) status = 4;
+
+    // exit: X, U, gains (the backward pass's, unscaled), scalars (LDS -> HBM)
+    const int Xo = cur ? L.X1 : L.X0, Uo = cur ? L.U1 : L.U0;
+    w.store_rec(a.X + prob * (int64_t)(n * (N + 1)), Xo, n, N + 1);
+    w.store_rec(a.U + prob * (int64_t)(m * N), Uo, m, N);
+    if (a.K) w.store_gains(a.K + prob * (int64_t)(m * n * N), a.k + prob * (int64_t)(m * N));
+    if (w.sl == 0) {
+      a.lamb[prob] = lamb;  // (every problem's: what the step-by-step form leaves there)
+      a.cost[prob] = cost_ret;
+      if (a.iters) a.iters[prob] = it;
+      if (a.status) a.status[prob] = status;
+    }
+    wave_sync();  // the exit's LDS reads are done before the next problem's entry overwrites them
+  }
+}
+
+I2LQR_WAVE_CHAIN_KERNELS(template __global__, double)
+I2LQR_WAVE_CHAIN_KERNELS(template __global__, float)
+
+namespace {
+
+template <class T, class Sys, bool HASQR>
+hipError_t launch_chain(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, int n_obs,
+                        const StateBox& box, size_t lds, hipStream_t s) {
+  constexpr int n = Sys::n;
+  const auto c = make_dev_cfg<T, Sys::n, Sys::m>(cfg);
+  BoxCfg<T, n> b;  // (as launch_box of i2lqr_wave_box.hip forms it)
+  for (int i = 0; i < n; i++) {
+    b.lo[i] = (T)box.lo[i];
+    b.hi[i] = (T)box.hi[i];
+  }
+  const T q1 = (T)box.q1;
+  b.q2 = (T)box.q2;
+  b.q12 = q1 * b.q2;
+  b.q122 = q1 * (b.q2 * b.q2);
+  b.m_lo = box.m_lo & ((1u << n) - 1);
+  b.m_hi = box.m_hi & ((1u << n) - 1);
+  lds += wave_box_lds_bytes(n_obs, n, cfg.N, sizeof(T));  // records, d1, d2 behind the slice
+  if (hipError_t e = raise_lds_limit<k_chain_box<T, Sys, HASQR>>(lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL((k_chain_box<T, Sys, HASQR>), dim3((unsigned)a.B), dim3(64), lds, s, c, a, steps,
+                     n_obs, b);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+template <class T>
+hipError_t wave_chain_solve(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, int n_obs,
+                            const StateBox& box, size_t lds, hipStream_t s) {
+  return visit_plant<T>(cfg, [&](auto, auto sys) {
+    using Sys = decltype(sys);
+    return has_stage_weights(cfg) ? launch_chain<T, Sys, true>(cfg, a, steps, n_obs, box, lds, s)
+                                  : launch_chain<T, Sys, false>(cfg, a, steps, n_obs, box, lds, s);
+  });
+}
+
+template hipError_t wave_chain_solve<double>(const i2lqr_config&, const IterArgs<double>&, int, int,
+                                             const StateBox&, size_t, hipStream_t);
+template hipError_t wave_chain_solve<float>(const i2lqr_config&, const IterArgs<float>&, int, int,
+                                            const StateBox&, size_t, hipStream_t);
+
+}  // namespace i2lqr

@@ -156,8 +156,10 @@ class BatchedILQR:
         problem-major layout: "group_lanes" (8 / 16 / 64), "speculate", "per_step_jacobians",
         "line_search" (2 / 4 / 8 step sizes per iteration on k_iterate_ls; 0 off), "obstacles"
         (K = 2 ... 8 obstacle records per problem on k_iterate_obs: `obs` is then [B, K, 6] and
-        shape("obs", B) says so; 0 off).  All but "wave_tail", "group_lanes", "line_search" and
-        "obstacles" leave the results bit-identical."""
+        shape("obs", B) says so; 0 off), "wave_chain" (1: solve_chained runs on k_chain_box, one
+        wavefront per chain, where the speculative chain kernel is not built - a state box,
+        "obstacles", "line_search", stage weights, quad12, ...; 0 off).  All but "wave_tail",
+        "group_lanes", "line_search" and "obstacles" leave the results bit-identical."""
         self._check(self.lib.i2lqr_set_option(self._handle, name.encode(), int(value)))
         if name == "obstacles":
             self.obstacles = int(value) if int(value) > 1 else 1
@@ -341,8 +343,12 @@ class BatchedILQR:
     def solve_chained(self, buf: dict, chains: int, chain_len: int) -> dict:
         """i2lqr_solve_chained: `chains` chains of `chain_len` problems each (problem-major buffers of
         chains * chain_len problems, chain after chain) solved in ONE launch, the final lamb of a
-        chain's problem c seeding its problem c + 1 (utils/base.py:393, :414-426).  Raises I2lqrError
-        (I2LQR_ERR_UNSUPPORTED) where the chain kernel is not built."""
+        chain's problem c seeding its problem c + 1 (utils/base.py:393, :414-426).  Runs on the
+        sixteen-lane speculative kernel (bicycles with Q = R = 0, one obstacle record, at most 512
+        chains, short horizons); with set_option("wave_chain", 1) everything else - a state box,
+        "obstacles", "line_search", stage weights, quad12, "group_lanes" 8 / 64, more chains, longer
+        horizons - runs on k_chain_box, one wavefront per chain.  Raises I2lqrError
+        (I2LQR_ERR_UNSUPPORTED) where neither is built or the option is off."""
         B = int(chains) * int(chain_len)
         if self.batch_of(buf["X"]) != B:
             raise ValueError(f"buffers hold {self.batch_of(buf['X'])} problems, {chains} chains of "

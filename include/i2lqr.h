@@ -350,8 +350,9 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     k_iterate_ls — one problem per wavefront, lane l rolls out candidate l mod
  *                     value, so the candidates share the one serial rollout k_iterate runs on all 64
  *                     lanes (three plants, both precisions, with or without stage weights);
- *                     i2lqr_iterate_pick takes its unfused form; i2lqr_solve_chained and a forced
- *                     "group_lanes" 8 or 16 answer I2LQR_ERR_UNSUPPORTED.  -1, 0 or 1: off (the
+ *                     i2lqr_iterate_pick takes its unfused form; i2lqr_solve_chained (unless
+ *                     "wave_chain" is 1) and a forced "group_lanes" 8 or 16 answer
+ *                     I2LQR_ERR_UNSUPPORTED.  -1, 0 or 1: off (the
  *                     default: the iteration above with one step is the reference's).  Any other
  *                     value is I2LQR_ERR_INVALID; a batch-minor / batch-tiled handle answers
  *                     I2LQR_ERR_UNSUPPORTED to 2, 4 or 8.
@@ -369,10 +370,27 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     call of the handle, whatever the batch size, runs on k_iterate_obs — one
  *                     problem per wavefront (three plants, both precisions, with or without stage
  *                     weights); together with "line_search" every iteration also tries that
- *                     option's step sizes.  i2lqr_backward, i2lqr_solve_chained and a forced
- *                     "group_lanes" 8 or 16 answer I2LQR_ERR_UNSUPPORTED.  -1, 0 or 1: off (the
+ *                     option's step sizes.  i2lqr_backward, i2lqr_solve_chained (unless
+ *                     "wave_chain" is 1) and a forced "group_lanes" 8 or 16 answer
+ *                     I2LQR_ERR_UNSUPPORTED.  -1, 0 or 1: off (the
  *                     default: obs[B][6]).  Any other value is I2LQR_ERR_INVALID; a batch-minor /
  *                     batch-tiled handle answers I2LQR_ERR_UNSUPPORTED to 2 ... 8.
+ *   "wave_chain"      1: where i2lqr_solve_chained would answer I2LQR_ERR_UNSUPPORTED on this
+ *                     (problem-major) handle - a state box, "obstacles" > 1, "line_search" > 1, stage
+ *                     weights, quad12, "group_lanes" 8 or 64, "speculate" 0, more than 512 chains, a
+ *                     horizon whose three-wavefront buffers do not fit - it runs k_chain_box instead:
+ *                     one wavefront per chain solves the chain's problems one after the other as
+ *                     k_iterate_box solves one (the handle's box, "obstacles" records and
+ *                     "line_search" step sizes; with none of them k_iterate's numbers), lamb carried
+ *                     in a register.  The results are those of chain_len calls of i2lqr_solve on a
+ *                     handle that runs k_iterate_box / k_iterate_obs / k_iterate_ls / k_iterate
+ *                     ("group_lanes" 64, "per_step_jacobians" 0), lamb copied across.  Where the
+ *                     speculative chain kernel is built it still runs: the option changes nothing
+ *                     there.  Still I2LQR_ERR_UNSUPPORTED: a horizon whose LDS need (the message
+ *                     names the bytes) exceeds the device's, and an opt-in model together with a
+ *                     forced "group_lanes" 8 or 16.  -1 or 0: off (the default: every refusal of
+ *                     i2lqr_solve_chained stays).  Any other value is I2LQR_ERR_INVALID; a
+ *                     batch-minor / batch-tiled handle answers I2LQR_ERR_UNSUPPORTED to 1.
  *   "stagger"         lane layouts (k_lane_iterate_rows, k_lane_iterate): every second half-thousand
  *                     of workgroups starts value x ~8000 cycles late, so that half of the
  *                     wavefronts stream their gains (forward pass) while the other half computes
@@ -405,8 +423,9 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value);
  * Rollouts, forward pass, line search, lamb schedule, status words and stored gains are unchanged.
  * While a bound is finite EVERY call of the handle, whatever the batch size, runs on k_iterate_box -
  * one problem per wavefront (three plants, both precisions, with or without stage weights); it
- * composes with "obstacles" and "line_search".  i2lqr_backward, i2lqr_solve_chained and a forced
- * "group_lanes" 8 or 16 answer I2LQR_ERR_UNSUPPORTED; i2lqr_iterate_pick takes its unfused form.
+ * composes with "obstacles" and "line_search".  i2lqr_backward, i2lqr_solve_chained (unless
+ * "wave_chain" is 1) and a forced "group_lanes" 8 or 16 answer I2LQR_ERR_UNSUPPORTED;
+ * i2lqr_iterate_pick takes its unfused form.
  * I2LQR_ERR_INVALID: a NaN bound, lo[i] >= hi[i], q1 <= 0 or q2 <= 0, exactly one pointer NULL.
  * I2LQR_ERR_UNSUPPORTED: a finite bound on a batch-minor / batch-tiled handle. */
 int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, double q1, double q2);
@@ -484,8 +503,10 @@ int i2lqr_solve(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term
  * speculative kernel solves its chains' problems one after the other: bit-identical to chain_len
  * calls of i2lqr_solve with lamb copied across, without their launches (~20 us each at N = 6).
  * I2LQR_ERR_UNSUPPORTED where that kernel is not built (stage weights, quad12, lane layouts, more
- * than 512 chains, a horizon whose three-wavefront buffers do not fit the LDS): solve the chain
- * steps one after the other instead (the Python host's HipCandidateSolver.solve_chained does).
+ * than 512 chains, a horizon whose three-wavefront buffers do not fit the LDS; a state box,
+ * "obstacles", "line_search") unless "wave_chain" is 1 - the chain then runs on k_chain_box, one
+ * wavefront per chain, with the same contract for lamb[] -: solve the chain steps one after the
+ * other instead (the Python host's HipCandidateSolver.solve_chained does).
  */
 int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void* X, void* U,
                         const void* x_term, void* lamb, const void* obs, void* cost, void* K, void* k,
