@@ -22,10 +22,7 @@
 #include "i2lqr_lane12.h"
 #include "i2lqr_rccl.hpp"
 #include "i2lqr_select.hpp"
-#include "i2lqr_wave_ls.h"
-#include "i2lqr_wave_box.h"
-#include "i2lqr_wave_chain.h"
-#include "i2lqr_wave_obs.h"
+#include "i2lqr_wave_opt.h"
 
 #define I2LQR_DRY_RUN_LANE 1
 #include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
@@ -171,10 +168,8 @@ struct i2lqr_handle {
   int opt_spec = -1;   // eight-lane kernel: speculative form (2-3 wavefronts per eight problems); -1 = automatic
   int opt_group_ws = -1;  // eight-lane kernel: workspace form (records / gains in HBM); -1 = automatic
   int opt_group_overlap = -1;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; -1 = automatic (on)
-  int opt_obs = 0;  // one-problem-per-wavefront kernel: obstacle records per problem (k_iterate_obs): 2 ... I2LQR_MAX_OBSTACLES; 0: off (one record)
-  i2lqr::StateBox box;  // one-problem-per-wavefront kernel: the state box (k_iterate_box, i2lqr_set_state_box); box.on(): some bound is finite
+  i2lqr::WaveModel model;  // one-problem-per-wavefront kernel: "line_search", "obstacles" and the state box (i2lqr_set_state_box), all off by default (i2lqr_wave_model.hpp)
   int opt_wave_chain = 0;  // i2lqr_solve_chained: 1 = what the speculative chain kernel is not built for runs on the one-problem-per-wavefront kernel's chained form (k_chain_box); 0: refused
-  int opt_ls = 0;  // one-problem-per-wavefront kernel: step sizes of the parallel line search (k_iterate_ls): 2, 4, 8; 0: off
   int opt_group_fixed = -1;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; -1 = automatic (on)
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
   // it into its kernel, otherwise the call runs the separate kernels.  The pointer to the call's
@@ -211,7 +206,7 @@ namespace {
 
 // Which fused kernel a problem-major call runs on: ONE function, used by the launchers and by
 // i2lqr_iterate_kernel / i2lqr_solve_kernel (what bench.py labels its results with).
-enum FusedKernel { K_WAVE, K_WAVE_LS, K_WAVE_OBS, K_WAVE_BOX, K_GROUP, K_GROUP16, K_GROUP_WS, K_SPEC, K_SPEC16, K_QUAD, K_INVALID };
+enum FusedKernel { K_WAVE, K_WAVE_OPT, K_GROUP, K_GROUP16, K_GROUP_WS, K_SPEC, K_SPEC16, K_QUAD, K_INVALID };
 // (measured on the 256-CU chip; DeviceGeometry::scaled() elsewhere)
 constexpr int64_t kAutoGroupBatch = 1024;  // eight-lane kernel from here (automatic)
 constexpr int64_t kAutoSpecBatch = 12288;  // speculative form for solves up to here (automatic)
@@ -220,36 +215,17 @@ constexpr int64_t kAutoSpecBatch = 12288;  // speculative form for solves up to 
 FusedKernel select_fused(const i2lqr_handle* h, int64_t B, bool early_exit, const char** why) {
   static const char* none = "";
   if (!why) why = &none;
-  // a state box (i2lqr_set_state_box): every call runs on the state-box form of the
-  // one-problem-per-wavefront kernel (k_iterate_box, i2lqr_wave_box.hip), whatever the batch size; it
-  // carries the obstacle records and the line search
-  if (h->box.on()) {
+  // a model is on ("line_search", "obstacles", a state box): every call runs on that form of the
+  // one-problem-per-wavefront kernel (i2lqr_wave_opt.h), whatever the batch size
+  if (const WaveForm f = h->model.form(); f != WAVE_PLAIN) {
     if (h->opt_group == 8 || h->opt_group == 16) {
-      *why = "a state box runs on the one-problem-per-wavefront kernel: not together with "
-             "\"group_lanes\" = 8 or 16";
+      static thread_local char msg[128];
+      snprintf(msg, sizeof(msg), "%s runs on the one-problem-per-wavefront kernel: not together "
+               "with \"group_lanes\" = 8 or 16", wave_phrase(f));
+      *why = msg;
       return K_INVALID;
     }
-    return K_WAVE_BOX;
-  }
-  // "obstacles": every call runs on the several-obstacles form of the one-problem-per-wavefront
-  // kernel (k_iterate_obs, i2lqr_wave_obs.hip), whatever the batch size; it carries the line search
-  if (h->opt_obs > 1) {
-    if (h->opt_group == 8 || h->opt_group == 16) {
-      *why = "\"obstacles\" runs on the one-problem-per-wavefront kernel: not together with "
-             "\"group_lanes\" = 8 or 16";
-      return K_INVALID;
-    }
-    return K_WAVE_OBS;
-  }
-  // "line_search": every call runs on the line-search form of the one-problem-per-wavefront kernel
-  // (k_iterate_ls, i2lqr_wave_ls.hip), whatever the batch size
-  if (h->opt_ls > 1) {
-    if (h->opt_group == 8 || h->opt_group == 16) {
-      *why = "\"line_search\" runs on the one-problem-per-wavefront kernel: not together with "
-             "\"group_lanes\" = 8 or 16";
-      return K_INVALID;
-    }
-    return K_WAVE_LS;
+    return K_WAVE_OPT;
   }
   const bool m2 = h->cfg.m == 2 && h->cfg.n + h->cfg.m <= 8;
   const bool q16 = h->cfg.n + h->cfg.m == 16;
@@ -340,6 +316,23 @@ FusedKernel select_fused(const i2lqr_handle* h, int64_t B, bool early_exit, cons
     return K_INVALID;
   }
   return K_WAVE;
+}
+
+// The opt-in form of a call (chained: k_chain_box) takes its records and the box's words behind the
+// handle's slice: I2LQR_OK if the sum fits the device's dynamic LDS, else the refusal with the bytes.
+int wave_lds_check(const i2lqr_handle* h, int n, size_t word, bool chained) {
+  const WaveForm f = h->model.form(chained);
+  const size_t need = h->lds_bytes + h->model.extra_lds_bytes(f, n, h->cfg.N, word);
+  if (need <= h->geo.max_dyn_lds) return I2LQR_OK;
+  const int n_obs = h->model.records();
+  char with[64];
+  if (f == WAVE_OBS)
+    snprintf(with, sizeof(with), "\"obstacles\" = %d", n_obs);
+  else
+    snprintf(with, sizeof(with), "%s and %d obstacle record%s",
+             chained ? "\"wave_chain\"" : wave_phrase(f), n_obs, n_obs > 1 ? "s" : "");
+  return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d with %s needs %zu B of LDS per wavefront (> %zu KiB)",
+              h->cfg.N, with, need, h->geo.max_dyn_lds / 1024);
 }
 
 // f(std::true_type()) for a device config with stage weights (DevCfg::flags), f(std::false_type())
@@ -458,28 +451,9 @@ template <class T, class Sys> struct Launch {
           return I2LQR_OK;
         }
         break;
-      case K_WAVE_BOX: {
-        const int n_obs = h->opt_obs > 1 ? h->opt_obs : 1;
-        const size_t need = h->lds_bytes + wave_box_lds_bytes(n_obs, n, h->cfg.N, sizeof(T));
-        if (need > h->geo.max_dyn_lds)
-          return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d with a state box and %d obstacle record%s "
-                      "needs %zu B of LDS per wavefront (> %zu KiB)", h->cfg.N, n_obs,
-                      n_obs > 1 ? "s" : "", need, h->geo.max_dyn_lds / 1024);
-        HIP_TRY(wave_box_iterate<T>(h->cfg, a, h->opt_ls > 1 ? h->opt_ls : 1, n_obs, h->box,
-                                    h->lds_bytes, s));
-        return I2LQR_OK;
-      }
-      case K_WAVE_OBS:
-        if (h->lds_bytes + wave_obs_lds_bytes(h->opt_obs, sizeof(T)) > h->geo.max_dyn_lds)
-          return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d with \"obstacles\" = %d needs %zu B of LDS "
-                      "per wavefront (> %zu KiB)", h->cfg.N, h->opt_obs,
-                      h->lds_bytes + wave_obs_lds_bytes(h->opt_obs, sizeof(T)),
-                      h->geo.max_dyn_lds / 1024);
-        HIP_TRY(wave_obs_iterate<T>(h->cfg, a, h->opt_ls > 1 ? h->opt_ls : 1, h->opt_obs,
-                                    h->lds_bytes, s));
-        return I2LQR_OK;
-      case K_WAVE_LS:
-        HIP_TRY(wave_ls_iterate<T>(h->cfg, a, h->opt_ls, h->lds_bytes, s));
+      case K_WAVE_OPT:
+        if (int rc = wave_lds_check(h, n, sizeof(T), false)) return rc;
+        HIP_TRY(wave_opt_launch<T>(h->cfg, a, h->model, false, h->lds_bytes, s));
         return I2LQR_OK;
       case K_WAVE:
         break;
@@ -508,56 +482,41 @@ template <class T, class Sys> struct Launch {
     return I2LQR_OK;
   }
   static int names_pair(i2lqr_handle*, int64_t, int) { return 0; }
-  // "wave_chain" 1: L chains of k problems each in one launch of k_chain_box (i2lqr_wave_chain.hip),
+  // L chains of k problems each in ONE launch: k_group_spec<.., CHAIN> where it is built for the
+  // handle; otherwise, and with a model on, "wave_chain" 1 runs k_chain_box (i2lqr_wave_chain.hip)
   // with the handle's state box, "obstacles" and "line_search"
-  static int wave_chain(i2lqr_handle* h, int64_t L, int k, void* X, void* U, const void* x_term,
-                        void* lamb, const void* obs, void* cost, void* K, void* kk, int32_t* iters,
-                        int32_t* status, hipStream_t s) {
-    const bool model = h->box.on() || h->opt_obs > 1 || h->opt_ls > 1;
-    if (model && (h->opt_group == 8 || h->opt_group == 16)) {  // (as i2lqr_solve refuses them)
-      const char* why = "";
-      (void)select_fused(h, L, true, &why);
-      return fail(I2LQR_ERR_UNSUPPORTED, "%s", why);
-    }
-    const int n_obs = h->opt_obs > 1 ? h->opt_obs : 1;
-    const size_t need = h->lds_bytes + wave_box_lds_bytes(n_obs, n, h->cfg.N, sizeof(T));
-    if (need > h->geo.max_dyn_lds)
-      return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d with \"wave_chain\" and %d obstacle record%s "
-                  "needs %zu B of LDS per wavefront (> %zu KiB)", h->cfg.N, n_obs,
-                  n_obs > 1 ? "s" : "", need, h->geo.max_dyn_lds / 1024);
-    IterArgs<T> a = iter_args<T>(L, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, kk, iters,
-                                 status);
-    a.chain_len = k;
-    HIP_TRY(wave_chain_solve<T>(h->cfg, a, h->opt_ls > 1 ? h->opt_ls : 1, n_obs, h->box,
-                                h->lds_bytes, s));
-    return I2LQR_OK;
-  }
-  // L chains of k problems each in ONE launch (k_group_spec<.., CHAIN>; "wave_chain" 1: k_chain_box
-  // where that kernel is not built for the handle)
   static int solve_chained(i2lqr_handle* h, int64_t L, int k, void* X, void* U, const void* x_term,
                            void* lamb, const void* obs, void* cost, void* K, void* kk, int32_t* iters,
                            int32_t* status, hipStream_t s) {
-    const bool wc = h->opt_wave_chain == 1;
-    if (wc && (h->box.on() || h->opt_obs > 1 || h->opt_ls > 1))
-      return wave_chain(h, L, k, X, U, x_term, lamb, obs, cost, K, kk, iters, status, s);
-    if constexpr (m == 2 && n + m <= 8) {
-      const bool spec = !(h->opt_spec == 0 || h->opt_group == 8 || h->opt_group == 64 ||
-                          !group_spec_chain_supported(h->cfg, L));
-      if (!spec && wc)
-        return wave_chain(h, L, k, X, U, x_term, lamb, obs, cost, K, kk, iters, status, s);
-      if (!spec)
-        return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel: a "
-                    "bicycle plant with Q = R = 0, at most %lld chains, a horizon whose three-wavefront "
-                    "buffers fit a CU's LDS (solve the chain steps one after the other instead)",
-                    (long long)h->geo.scaled(512));
-      IterArgs<T> a = iter_args<T>(L, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, kk, iters,
-                                   status);
-      a.chain_len = k;
-      HIP_TRY(group_spec_chain<T>(h->cfg, a, s));
-      return I2LQR_OK;
+    constexpr bool bicycle = m == 2 && n + m <= 8;
+    const bool wc = h->opt_wave_chain == 1, model = h->model.form() != WAVE_PLAIN;
+    bool spec = false;  // (not asked about where "wave_chain" takes the model anyway)
+    if constexpr (bicycle)
+      spec = !(wc && model) && !(h->opt_spec == 0 || h->opt_group == 8 || h->opt_group == 64 ||
+                                 !group_spec_chain_supported(h->cfg, L));
+    const bool wave = wc && (model || !spec);
+    if (!wave && !spec) {
+      if (!bicycle) return fail(I2LQR_ERR_UNSUPPORTED, "chains are built for the m = 2 plants");
+      return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel: a "
+                  "bicycle plant with Q = R = 0, at most %lld chains, a horizon whose three-wavefront "
+                  "buffers fit a CU's LDS (solve the chain steps one after the other instead)",
+                  (long long)h->geo.scaled(512));
     }
-    if (wc) return wave_chain(h, L, k, X, U, x_term, lamb, obs, cost, K, kk, iters, status, s);
-    return fail(I2LQR_ERR_UNSUPPORTED, "chains are built for the m = 2 plants");
+    if (wave) {
+      const char* why = "";  // a model with "group_lanes" 8 or 16: refused as i2lqr_solve refuses it
+      if (model && select_fused(h, L, true, &why) == K_INVALID)
+        return fail(I2LQR_ERR_UNSUPPORTED, "%s", why);
+      if (int rc = wave_lds_check(h, n, sizeof(T), true)) return rc;
+    }
+    IterArgs<T> a = iter_args<T>(L, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, kk, iters,
+                                 status);
+    a.chain_len = k;
+    if (wave) {
+      HIP_TRY(wave_opt_launch<T>(h->cfg, a, h->model, true, h->lds_bytes, s));
+    } else if constexpr (bicycle) {
+      HIP_TRY(group_spec_chain<T>(h->cfg, a, s));
+    }
+    return I2LQR_OK;
   }
   static int rollout(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term, void* cost,
                      hipStream_t s) {
@@ -1598,6 +1557,14 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch) {
   return I2LQR_OK;
 }
 
+// The opt-in forms exist on the one-problem-per-wavefront kernel only: switching `what` on is refused
+// on a handle of another layout.
+static bool problem_major(const i2lqr_handle* h) { return h->cfg.layout == I2LQR_LAYOUT_PROBLEM_MAJOR; }
+static int refuse_layout(const char* what) {
+  return fail(I2LQR_ERR_UNSUPPORTED, "%s is built for the problem-major layout (the "
+              "one-problem-per-wavefront kernel)", what);
+}
+
 int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   if (!h || !name) return fail(I2LQR_ERR_INVALID, "null handle or option name");
   if (value < -1 || value > 0x7fffffff) return fail(I2LQR_ERR_INVALID, "option value out of range");
@@ -1639,26 +1606,20 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   else if (!strcmp(name, "line_search")) {
     if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4 && v != 8)
       return fail(I2LQR_ERR_INVALID, "\"line_search\" is 2, 4 or 8 step sizes, or -1 / 0 / 1 (off)");
-    if (v > 1 && h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR)
-      return fail(I2LQR_ERR_UNSUPPORTED, "\"line_search\" is built for the problem-major layout (the "
-                  "one-problem-per-wavefront kernel)");
-    h->opt_ls = v > 1 ? v : 0;
+    if (v > 1 && !problem_major(h)) return refuse_layout(wave_phrase(WAVE_LS));
+    h->model.ls = v > 1 ? v : 0;
   }
   else if (!strcmp(name, "obstacles")) {
     if (v > I2LQR_MAX_OBSTACLES)
       return fail(I2LQR_ERR_INVALID, "\"obstacles\" is 2 ... %d records per problem, or -1 / 0 / 1 "
                   "(off: one record)", I2LQR_MAX_OBSTACLES);
-    if (v > 1 && h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR)
-      return fail(I2LQR_ERR_UNSUPPORTED, "\"obstacles\" is built for the problem-major layout (the "
-                  "one-problem-per-wavefront kernel)");
-    h->opt_obs = v > 1 ? v : 0;
+    if (v > 1 && !problem_major(h)) return refuse_layout(wave_phrase(WAVE_OBS));
+    h->model.obs = v > 1 ? v : 0;
   }
   else if (!strcmp(name, "wave_chain")) {
     if (v != -1 && v != 0 && v != 1)
       return fail(I2LQR_ERR_INVALID, "\"wave_chain\" is 1 (on), or -1 / 0 (off)");
-    if (v == 1 && h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR)
-      return fail(I2LQR_ERR_UNSUPPORTED, "\"wave_chain\" is built for the problem-major layout (the "
-                  "one-problem-per-wavefront kernel)");
+    if (v == 1 && !problem_major(h)) return refuse_layout("\"wave_chain\"");
     h->opt_wave_chain = v == 1 ? 1 : 0;
   }
   else if (!strcmp(name, "group_lanes")) {
@@ -1695,10 +1656,8 @@ int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, dou
       b.m_hi |= 1u << i;
     }
   }
-  if (b.on() && h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR)
-    return fail(I2LQR_ERR_UNSUPPORTED, "a state box is built for the problem-major layout (the "
-                "one-problem-per-wavefront kernel)");
-  h->box = b;
+  if (b.on() && !problem_major(h)) return refuse_layout(wave_phrase(WAVE_BOX));
+  h->model.box = b;
   return I2LQR_OK;
 }
 
@@ -1720,9 +1679,7 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
     case K_GROUP16: return "k_group_iterate (sixteen lanes)";
     case K_GROUP_WS: return "k_group_iterate (workspace form)";
     case K_QUAD: return "k_quad_iterate";
-    case K_WAVE_BOX: return "k_iterate (state box)";
-    case K_WAVE_OBS: return "k_iterate (several obstacles)";
-    case K_WAVE_LS: return "k_iterate (line search)";
+    case K_WAVE_OPT: return wave_kernel_name(h->model.form());
     case K_WAVE: return "k_iterate";
     default: return "unsupported";  // the launch returns I2LQR_ERR_UNSUPPORTED
   }
@@ -1756,12 +1713,9 @@ int i2lqr_backward(i2lqr_handle* h, int64_t B, const void* X, const void* U, con
   if (int rc = check_common(h, B)) return rc;
   if (B == 0) return I2LQR_OK;
   if (!X || !U || !x_term || !lamb || !K || !k) return fail(I2LQR_ERR_INVALID, "null buffer");
-  if (h->box.on())
-    return fail(I2LQR_ERR_UNSUPPORTED, "i2lqr_backward has no state box: clear it "
-                "(i2lqr_set_state_box with NULL bounds), or use i2lqr_iterate");
-  if (h->opt_obs > 1)
-    return fail(I2LQR_ERR_UNSUPPORTED, "i2lqr_backward reads one obstacle record per problem: "
-                "switch \"obstacles\" off, or use i2lqr_iterate");
+  // (k_backward has no forward pass: the line search does not concern it)
+  if (const WaveForm f = h->model.without_line_search().form(); f != WAVE_PLAIN)
+    return fail(I2LQR_ERR_UNSUPPORTED, "i2lqr_backward %s, or use i2lqr_iterate", wave_lack_phrase(f));
   const int rc = dispatch(h, [&](auto L) {
     return L.backward(h, B, X, U, x_term, lamb, obs, K, k, (hipStream_t)stream);
   });
@@ -1817,19 +1771,10 @@ int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void
   if (!X || !U || !x_term || !lamb || !cost) return fail(I2LQR_ERR_INVALID, "null buffer");
   if ((K == nullptr) != (k == nullptr))
     return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
-  const bool wc = h->opt_wave_chain == 1;  // (k_chain_box carries the three models refused below)
-  if (!wc && h->box.on())
-    return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which has "
-                "no state box: clear it (i2lqr_set_state_box with NULL bounds), or solve the chain "
-                "steps one after the other");
-  if (!wc && h->opt_obs > 1)
-    return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which reads "
-                "one obstacle record per problem: switch \"obstacles\" off, or solve the chain steps "
-                "one after the other");
-  if (!wc && h->opt_ls > 1)
-    return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which has "
-                "no line search: switch \"line_search\" off, or solve the chain steps one after the "
-                "other");
+  // (k_chain_box carries the models: nothing to refuse with "wave_chain" 1)
+  if (const WaveForm f = h->model.form(); f != WAVE_PLAIN && h->opt_wave_chain != 1)
+    return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which %s, "
+                "or solve the chain steps one after the other", wave_lack_phrase(f));
   const int rc = dispatch(h, [&](auto L) {
     return L.solve_chained(h, chains, chain_len, X, U, x_term, lamb, obs, cost, K, k, iters, status,
                            (hipStream_t)stream);

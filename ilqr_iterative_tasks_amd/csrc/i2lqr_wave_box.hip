@@ -19,13 +19,9 @@
 // issued with the phase's other reads.  Everything else - records, line search, accept / reject,
 // exit and stores - is k_iterate_obs's (i2lqr_wave_obs.hip), so the box composes with "obstacles"
 // and "line_search".
-#include "i2lqr_wave_box.h"
+#include "i2lqr_wave_opt.h"
 
 #include "i2lqr_wave_box.hpp"  // BoxWorker: ObsWorker with the box's prep
-#include "i2lqr_wave_obs.h"    // wave_obs_lds_bytes
-#include "i2lqr_geometry.hpp"
-#include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
-#include "i2lqr_group_launch.hpp"
 
 namespace i2lqr {
 
@@ -55,11 +51,11 @@ __global__ __launch_bounds__(64) void k_iterate_box(const DevCfg<T, Sys::n, Sys:
   const T* gob = a.obs ? a.obs + prob * (int64_t)(K * 6) : nullptr;  // this problem's obs[K][6]
 #pragma unroll
   for (int q = 0; q < 6; q++) ob[q] = gob ? gob[q] : T(q == 5 ? -1 : 1);
-  // ... and all K records behind the slice (wave_obs_lds_bytes; visible after the wave_sync below)
+  // ... and all K records behind the slice (extra_lds_bytes; visible after the wave_sync below)
   static_assert(I2LQR_MAX_OBSTACLES * 6 <= 64, "one record word per lane");
   T* recs = reinterpret_cast<T*>(smem_raw) + L.total;
   if (gob && lane < K * 6) recs[lane] = gob[lane];
-  T* bx = recs + K * 6;  // d1[N+1][n], d2[N+1][n], lo[n], hi[n] behind the records (wave_box_lds_bytes)
+  T* bx = recs + K * 6;  // d1[N+1][n], d2[N+1][n], lo[n], hi[n] behind the records (extra_lds_bytes)
   w.stage_box(box, bx);
   w.stage_consts();
   T lamb = a.lamb[prob];
@@ -144,49 +140,6 @@ __global__ __launch_bounds__(64) void k_iterate_box(const DevCfg<T, Sys::n, Sys:
   }
 }
 
-I2LQR_WAVE_BOX_KERNELS(template __global__, double)
-I2LQR_WAVE_BOX_KERNELS(template __global__, float)
-
-namespace {
-
-template <class T, class Sys, bool HASQR>
-hipError_t launch_box(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, int n_obs,
-                      const StateBox& box, size_t lds, hipStream_t s) {
-  constexpr int n = Sys::n;
-  const auto c = make_dev_cfg<T, Sys::n, Sys::m>(cfg);
-  BoxCfg<T, n> b;
-  for (int i = 0; i < n; i++) {
-    b.lo[i] = (T)box.lo[i];
-    b.hi[i] = (T)box.hi[i];
-  }
-  const T q1 = (T)box.q1;
-  b.q2 = (T)box.q2;
-  b.q12 = q1 * b.q2;  // (as make_dev_cfg forms ctrl_q12 / ctrl_q122)
-  b.q122 = q1 * (b.q2 * b.q2);
-  b.m_lo = box.m_lo & ((1u << n) - 1);
-  b.m_hi = box.m_hi & ((1u << n) - 1);
-  lds += wave_box_lds_bytes(n_obs, n, cfg.N, sizeof(T));  // records, d1, d2 behind the slice
-  if (hipError_t e = raise_lds_limit<k_iterate_box<T, Sys, HASQR>>(lds); e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_iterate_box<T, Sys, HASQR>), dim3((unsigned)a.B), dim3(64), lds, s, c, a,
-                     steps, n_obs, b);
-  return hipGetLastError();
-}
-
-}  // namespace
-
-template <class T>
-hipError_t wave_box_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, int n_obs,
-                            const StateBox& box, size_t lds, hipStream_t s) {
-  return visit_plant<T>(cfg, [&](auto, auto sys) {
-    using Sys = decltype(sys);
-    return has_stage_weights(cfg) ? launch_box<T, Sys, true>(cfg, a, steps, n_obs, box, lds, s)
-                                  : launch_box<T, Sys, false>(cfg, a, steps, n_obs, box, lds, s);
-  });
-}
-
-template hipError_t wave_box_iterate<double>(const i2lqr_config&, const IterArgs<double>&, int, int,
-                                             const StateBox&, size_t, hipStream_t);
-template hipError_t wave_box_iterate<float>(const i2lqr_config&, const IterArgs<float>&, int, int,
-                                            const StateBox&, size_t, hipStream_t);
+I2LQR_WAVE_OPT_KERNELS(template __global__, k_iterate_box, I2LQR_WAVE_TAIL_BOX)
 
 }  // namespace i2lqr

@@ -2,7 +2,7 @@
 // build on it: i2lqr_wave_box.hip (k_iterate_box: one problem per wavefront) and
 // i2lqr_wave_chain.hip (k_chain_box: a chain of problems per wavefront).
 #pragma once
-#include "i2lqr_wave_box.h"
+#include "i2lqr_wave_opt.h"  // BoxCfg
 #include "i2lqr_wave_obs.hpp"  // ObsWorker: LsWorker with the records' prep
 
 namespace i2lqr {

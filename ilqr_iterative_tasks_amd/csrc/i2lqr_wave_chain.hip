@@ -12,12 +12,9 @@
 // What differs: the problem index, the lamb load (first problem of the chain only), and the
 // wave_sync() that ends a problem - its exit stores read the trajectory and the gains from the LDS
 // that the next problem's entry overwrites.
-#include "i2lqr_wave_chain.h"
+#include "i2lqr_wave_opt.h"
 
 #include "i2lqr_wave_box.hpp"  // BoxWorker: ObsWorker with the box's prep
-#include "i2lqr_geometry.hpp"
-#include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
-#include "i2lqr_group_launch.hpp"
 
 namespace i2lqr {
 
@@ -37,7 +34,7 @@ __global__ __launch_bounds__(64) void k_chain_box(const DevCfg<T, Sys::n, Sys::m
   const int K = n_obs < 1 ? 1 : (n_obs > I2LQR_MAX_OBSTACLES ? I2LQR_MAX_OBSTACLES : n_obs);
   static_assert(I2LQR_MAX_OBSTACLES * 6 <= 64, "one record word per lane");
   T* recs = reinterpret_cast<T*>(smem_raw) + L.total;  // obs[K][6] behind the slice
-  T* bx = recs + K * 6;  // d1[N+1][n], d2[N+1][n], lo[n], hi[n] behind the records (wave_box_lds_bytes)
+  T* bx = recs + K * 6;  // d1[N+1][n], d2[N+1][n], lo[n], hi[n] behind the records (extra_lds_bytes)
   // once per kernel, the same for every problem of the chain: the bounds, Q_terminal
   w.stage_box(box, bx);
   w.stage_consts();
@@ -141,49 +138,6 @@ __global__ __launch_bounds__(64) void k_chain_box(const DevCfg<T, Sys::n, Sys::m
   }
 }
 
-I2LQR_WAVE_CHAIN_KERNELS(template __global__, double)
-I2LQR_WAVE_CHAIN_KERNELS(template __global__, float)
-
-namespace {
-
-template <class T, class Sys, bool HASQR>
-hipError_t launch_chain(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, int n_obs,
-                        const StateBox& box, size_t lds, hipStream_t s) {
-  constexpr int n = Sys::n;
-  const auto c = make_dev_cfg<T, Sys::n, Sys::m>(cfg);
-  BoxCfg<T, n> b;  // (as launch_box of i2lqr_wave_box.hip forms it)
-  for (int i = 0; i < n; i++) {
-    b.lo[i] = (T)box.lo[i];
-    b.hi[i] = (T)box.hi[i];
-  }
-  const T q1 = (T)box.q1;
-  b.q2 = (T)box.q2;
-  b.q12 = q1 * b.q2;
-  b.q122 = q1 * (b.q2 * b.q2);
-  b.m_lo = box.m_lo & ((1u << n) - 1);
-  b.m_hi = box.m_hi & ((1u << n) - 1);
-  lds += wave_box_lds_bytes(n_obs, n, cfg.N, sizeof(T));  // records, d1, d2 behind the slice
-  if (hipError_t e = raise_lds_limit<k_chain_box<T, Sys, HASQR>>(lds); e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_chain_box<T, Sys, HASQR>), dim3((unsigned)a.B), dim3(64), lds, s, c, a, steps,
-                     n_obs, b);
-  return hipGetLastError();
-}
-
-}  // namespace
-
-template <class T>
-hipError_t wave_chain_solve(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, int n_obs,
-                            const StateBox& box, size_t lds, hipStream_t s) {
-  return visit_plant<T>(cfg, [&](auto, auto sys) {
-    using Sys = decltype(sys);
-    return has_stage_weights(cfg) ? launch_chain<T, Sys, true>(cfg, a, steps, n_obs, box, lds, s)
-                                  : launch_chain<T, Sys, false>(cfg, a, steps, n_obs, box, lds, s);
-  });
-}
-
-template hipError_t wave_chain_solve<double>(const i2lqr_config&, const IterArgs<double>&, int, int,
-                                             const StateBox&, size_t, hipStream_t);
-template hipError_t wave_chain_solve<float>(const i2lqr_config&, const IterArgs<float>&, int, int,
-                                            const StateBox&, size_t, hipStream_t);
+I2LQR_WAVE_OPT_KERNELS(template __global__, k_chain_box, I2LQR_WAVE_TAIL_BOX)
 
 }  // namespace i2lqr

@@ -16,13 +16,9 @@
 // its trajectory as Worker::forward does; only an ACCEPTED iteration whose winner is a shorter step
 // repeats the rollout with that step on every lane (same code, same inputs: the same bits the
 // winning lanes computed).  No extra LDS.
-#include "i2lqr_wave_ls.h"
+#include "i2lqr_wave_opt.h"
 
 #include "i2lqr_wave_ls.hpp"  // LsWorker: Worker with the line search's forward pass
-#include "i2lqr_devcfg.hpp"
-#include "i2lqr_geometry.hpp"
-#include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
-#include "i2lqr_group_launch.hpp"
 
 namespace i2lqr {
 
@@ -128,33 +124,6 @@ __global__ __launch_bounds__(64) void k_iterate_ls(const DevCfg<T, Sys::n, Sys::
   }
 }
 
-namespace {
-
-template <class T, class Sys, bool HASQR>
-hipError_t launch_ls(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, size_t lds,
-                     hipStream_t s) {
-  const auto c = make_dev_cfg<T, Sys::n, Sys::m>(cfg);
-  if (hipError_t e = raise_lds_limit<k_iterate_ls<T, Sys, HASQR>>(lds); e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_iterate_ls<T, Sys, HASQR>), dim3((unsigned)a.B), dim3(64), lds, s, c, a,
-                     steps);
-  return hipGetLastError();
-}
-
-}  // namespace
-
-template <class T>
-hipError_t wave_ls_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, size_t lds,
-                           hipStream_t s) {
-  return visit_plant<T>(cfg, [&](auto, auto sys) {
-    using Sys = decltype(sys);
-    return has_stage_weights(cfg) ? launch_ls<T, Sys, true>(cfg, a, steps, lds, s)
-                                  : launch_ls<T, Sys, false>(cfg, a, steps, lds, s);
-  });
-}
-
-template hipError_t wave_ls_iterate<double>(const i2lqr_config&, const IterArgs<double>&, int, size_t,
-                                            hipStream_t);
-template hipError_t wave_ls_iterate<float>(const i2lqr_config&, const IterArgs<float>&, int, size_t,
-                                           hipStream_t);
+I2LQR_WAVE_OPT_KERNELS(template __global__, k_iterate_ls, I2LQR_WAVE_TAIL_LS)
 
 }  // namespace i2lqr

@@ -22,12 +22,9 @@
 // built.
 // Backward pass, forward pass (the line search's: `steps` = 1 is its one-candidate path), accept /
 // reject (whose cost has no barrier term), exit and stores are LsWorker's / Worker's, unchanged.
-#include "i2lqr_wave_obs.h"
+#include "i2lqr_wave_opt.h"
 
 #include "i2lqr_wave_obs.hpp"  // ObsWorker: LsWorker with the records' prep
-#include "i2lqr_geometry.hpp"
-#include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
-#include "i2lqr_group_launch.hpp"
 
 namespace i2lqr {
 
@@ -57,7 +54,7 @@ __global__ __launch_bounds__(64) void k_iterate_obs(const DevCfg<T, Sys::n, Sys:
   const T* gob = a.obs ? a.obs + prob * (int64_t)(K * 6) : nullptr;  // this problem's obs[K][6]
 #pragma unroll
   for (int q = 0; q < 6; q++) ob[q] = gob ? gob[q] : T(q == 5 ? -1 : 1);
-  // ... and all K records behind the slice (wave_obs_lds_bytes; visible after the wave_sync below)
+  // ... and all K records behind the slice (extra_lds_bytes; visible after the wave_sync below)
   static_assert(I2LQR_MAX_OBSTACLES * 6 <= 64, "one record word per lane");
   T* recs = reinterpret_cast<T*>(smem_raw) + L.total;
   if (gob && lane < K * 6) recs[lane] = gob[lane];
@@ -141,37 +138,6 @@ __global__ __launch_bounds__(64) void k_iterate_obs(const DevCfg<T, Sys::n, Sys:
   }
 }
 
-I2LQR_WAVE_OBS_KERNELS(template __global__, double)
-I2LQR_WAVE_OBS_KERNELS(template __global__, float)
-
-namespace {
-
-template <class T, class Sys, bool HASQR>
-hipError_t launch_obs(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, int n_obs,
-                      size_t lds, hipStream_t s) {
-  const auto c = make_dev_cfg<T, Sys::n, Sys::m>(cfg);
-  lds += wave_obs_lds_bytes(n_obs, sizeof(T));  // the records behind the slice
-  if (hipError_t e = raise_lds_limit<k_iterate_obs<T, Sys, HASQR>>(lds); e != hipSuccess) return e;
-  hipLaunchKernelGGL((k_iterate_obs<T, Sys, HASQR>), dim3((unsigned)a.B), dim3(64), lds, s, c, a,
-                     steps, n_obs);
-  return hipGetLastError();
-}
-
-}  // namespace
-
-template <class T>
-hipError_t wave_obs_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, int steps, int n_obs,
-                            size_t lds, hipStream_t s) {
-  return visit_plant<T>(cfg, [&](auto, auto sys) {
-    using Sys = decltype(sys);
-    return has_stage_weights(cfg) ? launch_obs<T, Sys, true>(cfg, a, steps, n_obs, lds, s)
-                                  : launch_obs<T, Sys, false>(cfg, a, steps, n_obs, lds, s);
-  });
-}
-
-template hipError_t wave_obs_iterate<double>(const i2lqr_config&, const IterArgs<double>&, int, int,
-                                             size_t, hipStream_t);
-template hipError_t wave_obs_iterate<float>(const i2lqr_config&, const IterArgs<float>&, int, int,
-                                            size_t, hipStream_t);
+I2LQR_WAVE_OPT_KERNELS(template __global__, k_iterate_obs, I2LQR_WAVE_TAIL_OBS)
 
 }  // namespace i2lqr

@@ -205,8 +205,8 @@ def test_refusals(torch_mod):
 
 
 def test_a_horizon_too_long_for_the_lds_names_its_bytes(torch_mod):
-    """wave_box_lds_bytes (csrc/i2lqr_wave_box.h) on top of the handle's slice against the device's
-    limit: quad12 in fp64 with eight records has the largest need per horizon step."""
+    """WaveModel::extra_lds_bytes (csrc/i2lqr_wave_model.hpp) on top of the handle's slice against the
+    device's limit: quad12 in fp64 with eight records has the largest need per horizon step."""
     from ilqr_iterative_tasks_amd import BatchedILQR, _abi, default_config, workloads
     from ilqr_iterative_tasks_amd.solver import I2lqrError
     torch_mod.cuda.current_device()

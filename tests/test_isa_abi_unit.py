@@ -39,3 +39,16 @@ def test_the_abi_unit_compiles_the_small_kernels_only(tmp_path):
     assert not moved, f"compiled into the ABI unit again (no extern template declaration?): {moved}"
     expect = sorted(SMALL * 2 + ["k_argmin_partial"] * 4)  # (k_argmin_partial: FINAL and not)
     assert sorted(names) == expect, sorted(names)
+
+
+def test_the_wave_opt_unit_compiles_no_kernel(tmp_path):
+    """csrc/i2lqr_wave_opt.hip is the host-only launcher of the opt-in wavefront kernels: it reaches
+    all 48 of them through the `extern template` list of csrc/i2lqr_wave_opt.h.  An instantiation
+    that list does not name would compile that kernel a second time, here."""
+    if not Path(HIPCC).exists():
+        pytest.skip("hipcc not available")
+    out = tmp_path / "i2lqr_wave_opt.s"
+    subprocess.run([HIPCC, *FLAGS, "-o", str(out), str(CSRC / "i2lqr_wave_opt.hip")], check=True,
+                   capture_output=True, timeout=900)
+    symbols = re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", out.read_text(), flags=re.M)
+    assert symbols == [], f"compiled into the launcher's unit (no extern template declaration?): {symbols}"

@@ -62,4 +62,7 @@ def test_header_documents_the_option_and_the_kernel_name():
     assert '"line_search"' in hdr
     assert '"k_iterate (line search)"' in hdr
     src = (ROOT / "ilqr_iterative_tasks_amd" / "csrc" / "i2lqr_abi.hip").read_text()
-    assert '!strcmp(name, "line_search")' in src and '"k_iterate (line search)"' in src
+    assert '!strcmp(name, "line_search")' in src and "wave_kernel_name(" in src
+    # (the names of the opt-in forms are written once, in the model's header)
+    model = (ROOT / "ilqr_iterative_tasks_amd" / "csrc" / "i2lqr_wave_model.hpp").read_text()
+    assert '"k_iterate (line search)"' in model

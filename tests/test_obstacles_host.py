@@ -179,4 +179,7 @@ def test_header_documents_the_option_and_the_kernel_name():
     hdr = (ROOT / "include" / "i2lqr.h").read_text()
     assert '"obstacles"' in hdr and "I2LQR_MAX_OBSTACLES 8" in hdr
     src = (ROOT / "ilqr_iterative_tasks_amd" / "csrc" / "i2lqr_abi.hip").read_text()
-    assert '!strcmp(name, "obstacles")' in src and '"k_iterate (several obstacles)"' in src
+    assert '!strcmp(name, "obstacles")' in src and "wave_kernel_name(" in src
+    # (the names of the opt-in forms are written once, in the model's header)
+    model = (ROOT / "ilqr_iterative_tasks_amd" / "csrc" / "i2lqr_wave_model.hpp").read_text()
+    assert '"k_iterate (several obstacles)"' in model

@@ -165,4 +165,7 @@ def test_header_documents_the_export_and_the_kernel_name():
     assert '"k_iterate (state box)"' in hdr and "control/ilqr_helper.py:59-64, 83-103" in hdr
     assert "i2lqr_set_state_box" in _abi.EXPORTS
     src = (ROOT / "ilqr_iterative_tasks_amd" / "csrc" / "i2lqr_abi.hip").read_text()
-    assert '"k_iterate (state box)"' in src
+    assert "wave_kernel_name(" in src
+    # (the names of the opt-in forms are written once, in the model's header)
+    model = (ROOT / "ilqr_iterative_tasks_amd" / "csrc" / "i2lqr_wave_model.hpp").read_text()
+    assert '"k_iterate (state box)"' in model
