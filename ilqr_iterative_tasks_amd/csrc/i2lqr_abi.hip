@@ -17,6 +17,7 @@
 #include "i2lqr_devcfg.hpp"
 #include "i2lqr_geometry.hpp"
 #include "i2lqr_group.h"
+#include "i2lqr_handle.hpp"
 #include "i2lqr_host.hpp"
 #include "i2lqr_kernels.h"
 #include "i2lqr_lane12.h"
@@ -24,8 +25,9 @@
 #include "i2lqr_select.hpp"
 #include "i2lqr_wave_opt.h"
 
-#define I2LQR_DRY_RUN_LANE 1
-#include "i2lqr_dryrun.hpp"  // (empty unless -DI2LQR_DRY_RUN: the ASan build)
+// LaneLaunch; brings in i2lqr_dryrun.hpp, whose macros record every launch below as well (empty
+// unless -DI2LQR_DRY_RUN: the ASan build)
+#include "i2lqr_lane_launch.hpp"
 
 using namespace i2lqr;
 
@@ -146,60 +148,8 @@ int debug_check(int rc, void* stream) {
 }
 }  // namespace
 
-struct i2lqr_handle {
-  i2lqr_config cfg;
-  int lanes;        // lanes of a wavefront that cooperate on one problem (1: batch-minor layout)
-  size_t lds_bytes; // dynamic LDS per workgroup (one wavefront)
-  int device;
-  void* ws = nullptr;  // caller-owned scratch of the batch-minor kernels
-  int64_t ws_bytes = 0;
-  int64_t compact_min_batch = -1;  // i2lqr_solve uses the chunked, compacting form from this batch; 0: never; -1: automatic
-  // scheduling options of the one-problem-per-lane kernels (i2lqr_set_option); -1 = automatic
-  int opt_defer = -1, opt_reroll = -1, opt_lds_steps = -1, opt_merge = -1, opt_ckpt = -1, opt_stagger = -1;
-  int wave_tail = -1;  // chunked solve: finish <= this many survivors with one problem per wavefront (0: off, -1: automatic)
-  int opt_pair = -1;  // bicycles' lane kernel (fp64 and fp32, with or without stage weights): workgroups of two wavefronts (main + helper); -1 = automatic
-  int opt_two_x = -1;  // ... its second state buffer (no re-roll of accepted steps); -1 = automatic
-  int opt_chunk_step = -1;  // chunked solve: length of the chunk that follows the first (automatic: 4); a schedule to measure against
-  int opt_fuse = -1;  // chunked solve: compaction folded into the chunk kernels' exit (round 6); 0: k_lane_compact launches; -1 = automatic (on)
-  int opt_final_round = -1;  // chunked solve: the round whose tail kernel takes every survivor and ends the schedule; 0: never; -1 = automatic
-  int opt_first_chunk = -1;  // chunked solve: pinned length of the first chunk, no extension chunks (a hand-tuned schedule to measure the data-driven one against); -1 = automatic
-  int opt_fstep = -1;  // one-problem-per-wavefront kernel: per-step Jacobian matrices in LDS; -1 = automatic
-  int opt_group = -1;  // problem-major layout: lanes per problem of the fused kernels: 8, 64; -1 = automatic
-  int opt_spec = -1;   // eight-lane kernel: speculative form (2-3 wavefronts per eight problems); -1 = automatic
-  int opt_group_ws = -1;  // eight-lane kernel: workspace form (records / gains in HBM); -1 = automatic
-  int opt_group_overlap = -1;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; -1 = automatic (on)
-  i2lqr::WaveModel model;  // one-problem-per-wavefront kernel: "line_search", "obstacles" and the state box (i2lqr_set_state_box), all off by default (i2lqr_wave_model.hpp)
-  int opt_wave_chain = 0;  // i2lqr_solve_chained: 1 = what the speculative chain kernel is not built for runs on the one-problem-per-wavefront kernel's chained form (k_chain_box); 0: refused
-  int opt_group_fixed = -1;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; -1 = automatic (on)
-  // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
-  // it into its kernel, otherwise the call runs the separate kernels.  The pointer to the call's
-  // epilogue is THREAD-LOCAL (t_epi below), not handle state: two host threads inside
-  // i2lqr_iterate_pick on one handle do not see each other's.
-  struct Epilogue {
-    const int32_t* qfun;
-    int outer_iter, max_relax_iter;
-    void* cost_it;
-    void* part;
-    int64_t* best_idx;
-    void* best_cost;
-    bool fused;
-  };
-  // Device words of the last-workgroup-done reduction (each wraps to 0 by itself when its launch
-  // has drawn all its tickets).  kTickets words, handed out round-robin: calls on one handle that
-  // are in flight at the same time (two streams) draw from different words as long as fewer than
-  // kTickets of them overlap; their part[] workspaces are the caller's and must differ.
-  static constexpr unsigned kTickets = 16;
-  unsigned* ticket = nullptr;
-  std::atomic<unsigned> ticket_next{0};
-  // i2lqr_sharded_round_flat: the event that orders the side stream behind the shard's solve and
-  // the one a later round waits for before it reuses the buffers (created on first use)
-  hipEvent_t ev_ready = nullptr, ev_side_done = nullptr;
-  bool side_pending = false;  // ev_side_done has been recorded at least once
-  DeviceGeometry geo;  // of h->device, queried in i2lqr_create (i2lqr_geometry.hpp)
-};
-
 namespace {
-thread_local i2lqr_handle::Epilogue* t_epi = nullptr;
+thread_local i2lqr_handle::Epilogue* t_epi = nullptr;  // (struct i2lqr_handle: i2lqr_handle.hpp)
 }
 
 namespace {
@@ -335,43 +285,14 @@ int wave_lds_check(const i2lqr_handle* h, int n, size_t word, bool chained) {
               h->cfg.N, with, need, h->geo.max_dyn_lds / 1024);
 }
 
-// f(std::true_type()) for a device config with stage weights (DevCfg::flags), f(std::false_type())
-// otherwise: the HASQR parameter of the kernel f launches.  BUILT = false where the stage-weight
-// instantiations do not exist (the caller has refused such a configuration): the false one always.
-template <bool BUILT = true, class F> void with_weights(int flags, F&& f) {
-  if constexpr (BUILT) {
-    if (flags) {
-      f(std::true_type());
-      return;
-    }
-  }
-  f(std::false_type());
-}
-
-// IterArgs of a launch on the caller's arrays, every optional field at its neutral value
-template <class T>
-IterArgs<T> iter_args(int64_t B, int n_iters, int early_exit, void* X, void* U, const void* x_term,
-                      void* lamb, const void* obs, void* cost, void* K, void* k, int32_t* iters,
-                      int32_t* status) {
-  IterArgs<T> a;
-  a.B = B; a.n_iters = n_iters; a.early_exit = early_exit;
-  a.X = (T*)X; a.U = (T*)U; a.x_term = (const T*)x_term; a.lamb = (T*)lamb; a.obs = (const T*)obs;
-  a.cost = (T*)cost; a.K = (T*)K; a.k = (T*)k; a.iters = iters; a.status = status;
-  a.dbg = nullptr;
-  a.count = nullptr; a.count_max = 0; a.max_total = 0; a.set_stride = 0;
-  return a;
-}
-
 // One launcher per (dtype, system); LANES fixed at 64 = one problem per wavefront.
 template <class T, class Sys> struct Launch {
   static constexpr int n = Sys::n, m = Sys::m, LANES = 64;
   using Cfg = DevCfg<T, n, m>;
 
   static size_t lds_bytes(int N) { return (size_t)Layout<Sys>(N).total * sizeof(T) * (64 / LANES); }
-  static size_t fstep_lds_bytes(int N) {
-    return (size_t)Layout<Sys>(N, true).total * sizeof(T) * (64 / LANES);
-  }
-  static constexpr bool kHasFstep = Sys::n <= 6;  // the bicycles; quad12's F is 1.5 KB per step
+  static size_t fstep_lds_bytes(int N) { return wave_fstep_lds_bytes<T, Sys>(N); }
+  static constexpr bool kHasFstep = kWaveHasFstep<Sys>;
   static unsigned grid(int64_t B) { return (unsigned)((B + (64 / LANES) - 1) / (64 / LANES)); }
 
   static int prepare(i2lqr_handle* h) {
@@ -391,17 +312,15 @@ template <class T, class Sys> struct Launch {
     return I2LQR_OK;
   }
 
-  static int iterate(i2lqr_handle* h, int64_t B, int n_iters, int early_exit, void* X, void* U,
-                     const void* x_term, void* lamb, const void* obs, void* cost, void* K, void* k,
-                     int32_t* iters, int32_t* status, hipStream_t s) {
+  static int iterate(i2lqr_handle* h, const SolveIO& io, hipStream_t s) {
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    IterArgs<T> a = iter_args<T>(B, n_iters, early_exit, X, U, x_term, lamb, obs, cost, K, k, iters,
-                                 status);
+    const int64_t B = io.B;
+    IterArgs<T> a = iter_args<T>(io);
 #ifdef I2LQR_STAMPS
     a.dbg = (unsigned long long*)h->ws;  // diagnostic build: caller registers [B][8] u64 here
 #endif
     const char* why = "";
-    const FusedKernel fk = select_fused(h, B, early_exit != 0, &why);
+    const FusedKernel fk = select_fused(h, B, io.early_exit != 0, &why);
     if (t_epi && (fk == K_GROUP || fk == K_GROUP16 || fk == K_GROUP_WS)) {  // the eight-lane kernels carry the epilogue
       a.qfun = t_epi->qfun;
       a.outer_iter = t_epi->outer_iter;
@@ -481,13 +400,12 @@ template <class T, class Sys> struct Launch {
     HIP_TRY(hipGetLastError());
     return I2LQR_OK;
   }
-  static int names_pair(i2lqr_handle*, int64_t, int) { return 0; }
-  // L chains of k problems each in ONE launch: k_group_spec<.., CHAIN> where it is built for the
+  static int names_pair(const i2lqr_handle*, int64_t, int) { return 0; }
+  // io.B chains of k problems each in ONE launch: k_group_spec<.., CHAIN> where it is built for the
   // handle; otherwise, and with a model on, "wave_chain" 1 runs k_chain_box (i2lqr_wave_chain.hip)
   // with the handle's state box, "obstacles" and "line_search"
-  static int solve_chained(i2lqr_handle* h, int64_t L, int k, void* X, void* U, const void* x_term,
-                           void* lamb, const void* obs, void* cost, void* K, void* kk, int32_t* iters,
-                           int32_t* status, hipStream_t s) {
+  static int solve_chained(i2lqr_handle* h, const SolveIO& io, int k, hipStream_t s) {
+    const int64_t L = io.B;
     constexpr bool bicycle = m == 2 && n + m <= 8;
     const bool wc = h->opt_wave_chain == 1, model = h->model.form() != WAVE_PLAIN;
     bool spec = false;  // (not asked about where "wave_chain" takes the model anyway)
@@ -508,8 +426,7 @@ template <class T, class Sys> struct Launch {
         return fail(I2LQR_ERR_UNSUPPORTED, "%s", why);
       if (int rc = wave_lds_check(h, n, sizeof(T), true)) return rc;
     }
-    IterArgs<T> a = iter_args<T>(L, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, kk, iters,
-                                 status);
+    IterArgs<T> a = iter_args<T>(io);
     a.chain_len = k;
     if (wave) {
       HIP_TRY(wave_opt_launch<T>(h->cfg, a, h->model, true, h->lds_bytes, s));
@@ -553,543 +470,6 @@ template <class T, class Sys> struct Launch {
   }
 };
 
-// Batch-minor / batch-tiled layouts: one problem per lane (i2lqr_lane.hpp).
-template <class T, class Sys, bool TILED> struct LaneLaunch {
-  // (measured on the 256-CU chip: DeviceGeometry::scaled() where they are used)
-  static constexpr int kAutoWaveTail = 2048;
-  static constexpr int kAutoSpecTail = 12288;  // (round 5: 8192; tools/solve_bench.py --plans)
-  static constexpr int64_t kAutoCompactBatch = 4096;
-  static constexpr int n = Sys::n, m = Sys::m, NT = Sys::NTRIG;
-  using Cfg = DevCfg<T, n, m>;
-  static unsigned grid(int64_t B) { return (unsigned)((B + 63) / 64); }
-  // the caller's arrays as a set (K, k, iters, status may be null)
-  static LaneSet<T> user_set(int64_t B, void* X, void* U, const void* x_term, void* lamb,
-                             const void* obs, void* cost, void* K, void* k, int32_t* iters,
-                             int32_t* status) {
-    return LaneSet<T>{(T*)X, (T*)U, (T*)x_term, (T*)obs, (T*)lamb, (T*)cost, (T*)K, (T*)k,
-                      iters, status, nullptr, B};
-  }
-  // the entry fields of a launch on the arrays of `w` (the caller's or a work set)
-  static void set_io(LaneArgs<T>& a, int n_iters, int early_exit, const LaneSet<T>& w) {
-    a.B = w.B; a.n_iters = n_iters; a.early_exit = early_exit;
-    a.X = w.X; a.U = w.U; a.x_term = w.x_term; a.lamb = w.lamb; a.obs = w.obs; a.cost = w.cost;
-    a.K = w.K; a.k = w.k; a.iters = w.iters; a.status = w.status;
-  }
-  // i2lqr_solve of B problems runs as the chunked solve (solve_compacting).  Automatic: from 4096
-  // problems with more than 16 iterations allowed (measured 1.2-1.9x on the bench workload from
-  // 4096 to 262144 problems; the chunks alone cost ~9 % when nothing terminates early).
-  static bool chunked(const i2lqr_handle* h, int64_t B) {
-    const int64_t cmin = h->compact_min_batch < 0
-        ? (h->cfg.max_iter > 16 ? h->geo.scaled(kAutoCompactBatch) : 0) : h->compact_min_batch;
-    return cmin > 0 && B >= cmin && h->cfg.max_iter > 4;
-  }
-  // Workspace (bytes) for B problems: candidate trajectory + gains scratch (every call), and for
-  // the chunked solve two compacted work sets, scratch iters/status and one counter per round.
-  static constexpr int kMaxRounds = 24;  // compaction rounds of the chunked solve (one counter each)
-  static constexpr int kFirstChunk = 8;
-  static constexpr int kFinalRound = 3;  // chunked solve: the round (at 24 iterations) whose tail takes everything
-  static int64_t set_words(int N) { return (int64_t)(n * (N + 1) + m * N + n + 6 + 2); }
-  static int64_t ws_bytes(int N, int64_t B) {
-    const int64_t Bp = TILED ? (B + 63) / 64 * 64 : B;
-    // (+ the second state buffer of the helper-wavefront form: its own rows since round 6 — the
-    // chunks' exits pack survivors into the work set the chunk does not run on, which used to lend
-    // its states)
-    const int64_t words = lane_workspace_words<Sys>(N, Bp) + 2 * set_words(N) * Bp +
-                          Bp * (int64_t)(n * (N + 1));
-    return words * (int64_t)sizeof(T) + (2 * 3 + 2) * Bp * 4 + 16 + kMaxRounds * 4;
-  }
-  static int prepare(i2lqr_handle* h) {
-    h->lanes = 1;
-    h->lds_bytes = 0;
-    return I2LQR_OK;
-  }
-  // stage weights Q, R != 0: the bicycles in both precisions; the row-block plant (quad12) in fp64
-  // (round 5: instantiations of their own, i2lqr_lane12qr.hip)
-  static constexpr bool kStageWeights = Sys::NBLK == 0 || sizeof(T) == 8;
-  static int need_ws(i2lqr_handle* h, int64_t B) {
-    if (!kStageWeights && has_stage_weights(h->cfg))
-      return fail(I2LQR_ERR_UNSUPPORTED, "the one-problem-per-lane kernels of this plant are built "
-                  "for Q = R = 0 (use the problem-major layout for stage weights)");
-    if (TILED && (B & 63))
-      return fail(I2LQR_ERR_INVALID, "the batch-tiled layout needs a batch that is a multiple of "
-                  "64 (got %lld)", (long long)B);
-    const int64_t need = ws_bytes(h->cfg.N, B);
-    if (!h->ws || h->ws_bytes < need)
-      return fail(I2LQR_ERR_INVALID, "workspace of %lld B registered, batch %lld needs %lld B "
-                  "(i2lqr_workspace_bytes / i2lqr_set_workspace)", (long long)h->ws_bytes,
-                  (long long)B, (long long)need);
-    return I2LQR_OK;
-  }
-  struct Carved {
-    LaneSet<T> set[2];
-    int32_t* uiters;
-    int32_t* ustatus;
-    int32_t* count;  // [kMaxRounds]: the live count after each compaction round
-  };
-  static void carve(i2lqr_handle* h, int64_t B, LaneArgs<T>& a, Carved* cv = nullptr) {
-    const int N = h->cfg.N;
-    // (no workspace registered: names_pair() carves on scratch arguments that are never launched —
-    // a non-null base keeps the pointer arithmetic defined)
-    static char no_ws[16];
-    T* p = (T*)(h->ws ? h->ws : (void*)no_ws);
-    a.wsU = p; p += B * (int64_t)(m * N);
-    a.wsK = p; p += B * (int64_t)(m * n * N);
-    a.wsk = p; p += B * (int64_t)(m * N);
-    // second state buffer of the helper-wavefront form (rows of its own behind the gains scratch)
-    a.wsX = h->opt_two_x != 0 ? p : nullptr;
-    p += B * (int64_t)(n * (N + 1));
-    a.two_max = 64 * (int)(h->opt_two_x == 1 ? pair_max_grid(h->geo) : two_x_max_grid(h->geo));
-    a.count_lo = -1;
-    a.count_hi = 0x7fffffff;
-    a.count = nullptr;
-    a.resume = 0;
-    a.max_total = 0x7fffffff;
-    // The gains of the first steps stay in LDS: as many steps as keep the register-limited number
-    // of wavefronts per CU (one per SIMD, four per CU) resident in the 160 KiB: 36 KiB each, i.e.
-    // 5 steps in fp64 and 10 in fp32 at n=6, m=2.
-    const int per_step = 64 * m * (n + 1) * (int)sizeof(T);
-    a.lds_steps = ((int)h->geo.lds_per_simd_wave() - kK0Bytes) / per_step;  // steps 1..lds_steps; k_0 sits behind them
-    if (a.lds_steps < 0) a.lds_steps = 0;
-    if (a.lds_steps > N - 1) a.lds_steps = N - 1;
-    // (batch sizes in units of the chip: full = one wavefront per SIMD, 65536 problems on 256 CUs)
-    const int64_t full = h->geo.full_batch();
-    a.reroll = B >= full / 2 ? 1 : 0;  // pays only where the kernel sits on the HBM roof (32768)
-    a.defer = 1;  // the forward pass stores no states; accepted steps re-roll them (see i2lqr_lane.hpp)
-    // ... and merge the accepted candidate inputs into the one input buffer.  fp64 (HBM-bound):
-    // 7.56 -> 7.23 KB per problem-iteration, +4.8 % it/s at 2^20 problems; fp32 (instruction-bound):
-    // the extra row writes cost 6 %, so the per-lane buffer swap stays (tools/ab_bench.py).  Below
-    // ~40000 problems the fp64 kernel is instruction-bound as well (one or two wavefronts per CU):
-    // 226 -> 237 M it/s at 12800 problems without the merge, 411 -> 426 at 24576, 528 -> 545 at
-    // 32768, +-0 from 40960 to 57344, 811 -> 846 WITH it at 65536.
-    a.merge = sizeof(T) == 8 && B > full / 2 ? 1 : 0;
-    if (h->opt_merge >= 0) a.merge = h->opt_merge;
-    a.ckpt = 0;  // decided in finish_options() once the other options are final
-    a.stagger = 0;
-    std::memset(&a.cp, 0, sizeof(a.cp));  // plain exit; solve_compacting() fills it per chunk
-    if constexpr (Sys::NBLK > 0) {
-      // automatic where the launch fills the chip (one wavefront per SIMD: 65536 problems)
-      a.stagger = B >= full ? 45 : 0;
-    } else if (sizeof(T) == 8 && B > full * 15 / 16 && B <= full * 5 / 4) {
-      // bicycles, fp64, a launch of about one wavefront per SIMD: +3 % (883 -> 912 M it/s at 65536
-      // problems, tools/ab_bench.py --cold); fp32 (issue-bound) gains nothing, launches of two
-      // and more rounds desynchronise by themselves and only pay the delay (-2 %)
-      a.stagger = 8;
-    }
-    if (h->opt_stagger >= 0) a.stagger = h->opt_stagger > 999 ? 999 : h->opt_stagger;
-    a.dbg = nullptr;
-#ifdef I2LQR_STAMPS
-    if (const char* e = getenv("I2LQR_DBG_PTR")) a.dbg = (unsigned long long*)strtoull(e, nullptr, 0);
-#endif
-    if (h->opt_reroll >= 0) a.reroll = h->opt_reroll;
-    if (h->opt_defer >= 0) a.defer = h->opt_defer;
-    if (h->opt_lds_steps >= 0 && h->opt_lds_steps < a.lds_steps) a.lds_steps = h->opt_lds_steps;
-    a.lds_grow = h->opt_lds_steps < 0 ? 1 : 0;
-    finish_options(h, B, a);
-    if (!cv) return;
-    for (int q = 0; q < 2; q++) {
-      LaneSet<T>& st = cv->set[q];
-      st.B = B;
-      st.X = p; p += B * (int64_t)(n * (N + 1));
-      st.U = p; p += B * (int64_t)(m * N);
-      st.x_term = p; p += B * n;
-      st.obs = p; p += B * 6;
-      st.lamb = p; p += B;
-      st.cost = p; p += B;
-      st.K = a.wsK;
-      st.k = a.wsk;
-    }
-    int32_t* ip = (int32_t*)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-    for (int q = 0; q < 2; q++) {
-      cv->set[q].iters = ip; ip += B;
-      cv->set[q].status = ip; ip += B;
-      cv->set[q].orig = ip; ip += B;
-    }
-    cv->uiters = ip; ip += B;
-    cv->ustatus = ip; ip += B;
-    cv->count = ip;
-  }
-  // LDS of the state checkpointing: the states of one segment of kSeg steps for 64 lanes
-  static constexpr int kSegBytes = (kSeg + 1) * n * 64 * (int)sizeof(T);
-  // k_0 of 64 lanes: step 0 keeps only its feed-forward term in LDS (LaneWorker::lds_k0)
-  static constexpr int kK0Bytes = 64 * m * (int)sizeof(T);
-  // State checkpointing (i2lqr_lane.hpp): fp64 with deferred, merged states and the re-rolling
-  // forward pass, Q = R = 0; automatic from 65536 problems (where the kernel sits on the HBM
-  // roof).  Its segment buffer takes the place of LDS-resident gain steps.  Must be called again
-  // after any later change of defer / reroll / merge (the early-exit path does).
-  static void finish_options(const i2lqr_handle* h, int64_t B, LaneArgs<T>& a) {
-    const bool can = sizeof(T) == 8 && !has_stage_weights(h->cfg) && a.defer && a.merge && a.reroll &&
-                     h->cfg.N >= 2;
-    // (tools/ab_bench.py --cold, round 3: -2 % at 65536 problems, +-0 at 131072, +5 % at 262144,
-    // +4-6 % at 2^20; HBM bytes per problem-iteration 6993 -> 6243 (1.41 -> 1.26 x algorithmic):
-    // on from 65536 problems, BASELINE's roofline batch and half a per-GPU shard of configs[3] —
-    // where the kernel already sits on the HBM roof the bytes are what is left to win)
-    a.ckpt = can && (h->opt_ckpt >= 0 ? h->opt_ckpt != 0 : B >= h->geo.full_batch());
-    if (a.ckpt) {
-      const int per_step = 64 * m * (n + 1) * (int)sizeof(T);
-      int steps = ((int)h->geo.lds_per_simd_wave() + 1024 - kSegBytes - kK0Bytes) / per_step;
-      if (steps < 0) steps = 0;
-      if (a.lds_steps > steps) a.lds_steps = steps;
-    }
-  }
-  // The helper-wavefront form (k_lane_iterate_pair; round 5): the bicycles in fp64 and fp32 (stage
-  // weights: its HASQR instantiations), states not checkpointed, and a launch of at most 512 workgroups (32768 problems) - two wavefronts per
-  // workgroup then still find a SIMD each.  Properties of the chip: half as many workgroups as it
-  // has SIMDs (512 on 256 CUs); the second state buffer up to one workgroup per CU.
-  static unsigned pair_max_grid(const DeviceGeometry& g) { return (unsigned)(g.simds() / 2); }
-  static unsigned two_x_max_grid(const DeviceGeometry& g) { return (unsigned)g.cus; }
-  static bool pair_built(const Cfg& c, const LaneArgs<T>& a, int opt_pair) {
-    if constexpr (Sys::NBLK == 0) return !a.ckpt && opt_pair != 0;
-    return false;
-  }
-  static bool use_pair(const DeviceGeometry& g, const Cfg& c, const LaneArgs<T>& a, int64_t B,
-                       int opt_pair) {
-    return pair_built(c, a, opt_pair) && (opt_pair == 1 || grid(B) <= pair_max_grid(g));
-  }
-  static size_t lane_lds(const LaneArgs<T>& a) {
-    return (size_t)a.lds_steps * 64 * m * (n + 1) * sizeof(T) + kK0Bytes + (a.ckpt ? kSegBytes : 0);
-  }
-  // A launch of at most 256 / 512 workgroups puts one / two of them on a CU, so each has 160 / 80
-  // KiB of LDS to itself where a full launch budgets 36 (four wavefronts per CU): the gains of that
-  // many more horizon steps stay in LDS between the backward and the forward pass instead of going
-  // through HBM (fp64, n = 6, m = 2: 19 of 20 steps up to 256 workgroups, 8-10 up to 512).
-  // lds_steps of a launch of `workgroups` workgroups with `fixed` bytes of other dynamic LDS each,
-  // at most max_dyn bytes of dynamic LDS per workgroup
-  static int grown_lds_steps(const DeviceGeometry& g, const Cfg& c, const LaneArgs<T>& a,
-                             unsigned workgroups, size_t fixed, size_t max_dyn) {
-    if (!a.lds_grow || a.ckpt) return a.lds_steps;
-    const unsigned per_cu = (workgroups + (unsigned)g.cus - 1) / (unsigned)g.cus;
-    size_t budget = g.lds_per_cu / (per_cu ? per_cu : 1);
-    if (budget > max_dyn) budget = max_dyn;
-    const size_t per_step = (size_t)64 * m * (n + 1) * sizeof(T);
-    const size_t need0 = fixed + kK0Bytes + 1024;  // (1 KiB: allocation granularity)
-    int steps = budget > need0 ? (int)((budget - need0) / per_step) : 0;
-    if (steps > c.N - 1) steps = c.N - 1;
-    return steps > a.lds_steps ? steps : a.lds_steps;
-  }
-  // More than 64 KiB of dynamic LDS per workgroup has to be asked for; the attribute belongs to
-  // the kernel ON THE CURRENT DEVICE, so it is set by every launch that needs it (a process may
-  // drive several devices) and a refusal falls back to what 64 KiB hold.
-  template <class K>
-  static void grow_lds(const DeviceGeometry& g, K kernel, const Cfg& c, LaneArgs<T>& a,
-                       unsigned workgroups, size_t fixed) {
-    const int before = a.lds_steps;
-    a.lds_steps = grown_lds_steps(g, c, a, workgroups, fixed, g.max_dyn_lds);
-    if (lane_lds(a) + fixed <= g.default_dyn_lds) return;
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)g.max_dyn_lds) == hipSuccess)
-      return;
-    (void)hipGetLastError();
-    a.lds_steps = before;
-    a.lds_steps = grown_lds_steps(g, c, a, workgroups, fixed, g.default_dyn_lds);
-  }
-  template <bool TL>
-  static void launch_pair(const DeviceGeometry& g, const Cfg& c, const LaneArgs<T>& a,
-                          unsigned workgroups, hipStream_t s) {
-    if constexpr (Sys::NBLK == 0) {
-      LaneArgs<T> ap = a;
-      // stage weights: the record carries 2 Q (x_t - xtarget) as well
-      with_weights(c.flags, [&](auto W) {
-        using LW = LaneWorker<T, Sys, W, TL>;
-        const size_t fixed = 2 * LW::kRec * 64 * sizeof(T) + 65 * sizeof(int) + 12;
-        grow_lds(g, &k_lane_iterate_pair<T, Sys, W, TL>, c, ap, workgroups, fixed);
-        hipLaunchKernelGGL((k_lane_iterate_pair<T, Sys, W, TL>), dim3(workgroups), dim3(128),
-                           lane_lds(ap) + fixed, s, c, ap);
-      });
-    }
-  }
-  template <bool TL>
-  static void launch_iterate(const DeviceGeometry& g, const Cfg& c, const LaneArgs<T>& a, int64_t B,
-                             hipStream_t s, int opt_pair = 0) {
-    if (use_pair(g, c, a, B, opt_pair)) {
-      launch_pair<TL>(g, c, a, grid(B), s);
-      return;
-    }
-    if constexpr (Sys::NBLK > 0) {  // row-block plants: their own fused kernel, no LDS
-      with_weights<kStageWeights>(c.flags, [&](auto W) {
-        hipLaunchKernelGGL((k_lane_iterate_rows<T, Sys, W, TL>), dim3(grid(B)), dim3(64), 0, s, c, a);
-      });
-    } else {
-      LaneArgs<T> ag = a;
-      with_weights(c.flags, [&](auto W) {
-        grow_lds(g, &k_lane_iterate<T, Sys, W, TL>, c, ag, grid(B), 0);
-        hipLaunchKernelGGL((k_lane_iterate<T, Sys, W, TL>), dim3(grid(B)), dim3(64), lane_lds(ag), s,
-                           c, ag);
-      });
-    }
-  }
-
-  // The schedule of the chunked solve is STRUCTURAL and its decisions are the device's (round 5;
-  // VERDICT r4 #3 — round 4 sized the first chunk from the bench workload's survivor curve, a
-  // constant fitted to workloads.make_batch): a first chunk of kFirstChunk iterations on the whole
-  // batch (never shorter: the tail kernel sums in another order than the lane kernels, and the
-  // more iterations of a long-horizon problem it runs the further the two solves drift apart in
-  // the last digits — 2.3e-8 relative at N = 50 with a first chunk of 6 against the suite's 1e-8),
-  // then rounds of { compaction, tail kernel, lane chunk } with chunk lengths 4, then as many
-  // iterations as are done (compaction points 8, 12, 24, 48, 96).  Which of the two kernels of a
-  // round does the work is decided ON THE DEVICE from the live count the compaction leaves: the
-  // tail kernel is a no-op above its cap ("wave_tail"), the lane chunk skips what the tail has
-  // finished.  Measured against hand-tuned first chunks of 8 / 10 / 12 / 14 on three
-  // distributions (the bench's; every problem with the obstacle; targets twice as far) at
-  // 16384 ... 262144 problems (tools/solve_bench.py --plans, profiles/r05_solve_schedule.txt):
-  // within 15 % of the best hand-tuned schedule in all 18 cases (worst: 32768 problems, every
-  // problem with the obstacle, 1.144; 65536: 1.033 / 1.081 / 1.062).  Tried and dropped: up to three in-place
-  // extension chunks of 2 iterations gated on the survivor count of the chunk before (ahead at
-  // <= 32768 problems on the hard distribution, 13-41 % behind from 131072, where a chunk over
-  // the whole batch is several rounds of wavefronts); chunks of 2 behind the first.
-  // Chunked solve with compaction (large batches): ilqr() runs 1..max_iter iterations per
-  // problem, so a wavefront of 64 problems would otherwise idle on its slowest lane.  The batch
-  // is solved in chunks of 8, 4, then doubling; after every chunk the terminated problems
-  // are scattered to the caller's arrays and the survivors are packed into a dense work set
-  // (k_lane_compact).  No host synchronisation: the live count stays in device memory and
-  // surplus wavefronts exit at once.  Results are bit-identical to the plain launch.
-  static int solve_compacting(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term,
-                              void* lamb, const void* obs, void* cost, void* K, void* k,
-                              int32_t* iters, int32_t* status, hipStream_t s) {
-    if (int rc = need_ws(h, B)) return rc;
-    const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    const int N = h->cfg.N, max_iter = h->cfg.max_iter;
-    LaneArgs<T> a0;
-    Carved cv;
-    carve(h, B, a0, &cv);
-    LaneSet<T> usr = user_set(B, X, U, x_term, lamb, obs, cost, K, k, iters, status);
-    if (!iters) usr.iters = cv.uiters;
-    if (!status) usr.status = cv.ustatus;
-    if (!obs) { cv.set[0].obs = nullptr; cv.set[1].obs = nullptr; }
-    // Latency tail: once few problems survive, the rest of the solve is bound by the slowest
-    // problem's iteration latency, which is ~2.8x lower with one problem per WAVEFRONT.  If the
-    // packed set holds <= wave_tail problems the one-problem-per-wavefront kernel finishes them
-    // (it reads the live count itself and is a no-op otherwise); the lane chunks that follow skip
-    // finished problems and the next compaction scatters them to the caller.
-    // The survivors are the problems with long accept / reject chains (stragglers alternate
-    // accept, reject, accept, ...): the speculative sixteen-lane kernel runs the iteration after
-    // a reject beside the current one and needs about half the rounds; bit-identical to the
-    // plain kernel.  It takes over from 12288 survivors (workgroups of four problems whose slowest
-    // member decides; the hardware backfills), the one-problem-per-wavefront kernel (other
-    // plants, stage weights) from 2048.
-    bool spec_tail = false;
-    if constexpr (m == 2 && n + m <= 8)
-      spec_tail = h->opt_spec != 0 && c.flags == 0 && group_spec_tail_supported(h->cfg);
-    const int wave_tail = h->wave_tail < 0
-        ? (int)h->geo.scaled(spec_tail ? kAutoSpecTail : kAutoWaveTail) : h->wave_tail;
-    // chunk 0 runs in place on the caller's arrays
-    const int first = h->opt_first_chunk > 0 ? h->opt_first_chunk : kFirstChunk;
-    int done = 0, len = max_iter < first ? max_iter : first;
-    const int step = h->opt_chunk_step > 0 ? h->opt_chunk_step : 4;
-    set_io(a0, len, 1, usr);
-    a0.max_total = max_iter;
-    // one live counter per compaction round, all cleared by ONE fill in front of the first chunk (a
-    // fill per round was a 5 us launch of its own in each of the rounds that follow the tail)
-    HIP_TRY(hipMemsetAsync(cv.count, 0, kMaxRounds * sizeof(int32_t), s));
-    // Round 6: the compaction is folded into the chunk kernels' EXIT (LaneCompact: a wavefront that
-    // has finished its chunk packs its survivors into the next work set and scatters what
-    // terminated, one atomic add per wavefront, while the other wavefronts still iterate) — the
-    // k_lane_compact launch between every two chunks and the final scatter pass are gone
-    // ("fused_compaction" 0 brings them back: the A/B and the fallback).
-    const bool fused = h->opt_fuse != 0;
-    auto plan_exit = [&](LaneArgs<T>& a, bool src_user, const int32_t* orig, LaneSet<T>* dst,
-                         int32_t* count_out) {
-      std::memset(&a.cp, 0, sizeof(a.cp));
-      if (!fused) return;
-      a.cp.on = 1;
-      a.cp.src_is_user = src_user ? 1 : 0;
-      a.cp.user_tiled = TILED ? 1 : 0;
-      a.cp.orig = orig;
-      if (dst) a.cp.dst = *dst;
-      a.cp.count_out = count_out;
-      a.cp.usr = usr;
-    };
-    int round = 0;  // counter of the work set the NEXT compaction fills
-    int cur = 0;    // ... and its index
-    const bool only_chunk = len >= max_iter;  // (max_iter <= first chunk: nothing survives it)
-    plan_exit(a0, true, nullptr, only_chunk ? nullptr : &cv.set[cur], cv.count + round);
-    launch_iterate<TILED>(h->geo, c, a0, B, s, h->opt_pair);
-    done += len;
-    const unsigned cgrid = (unsigned)((B + 255) / 256);
-    bool src_user = true;
-    const int32_t* count_in = nullptr;
-    LaneSet<T> src = usr;
-    // The LAST round (automatic: the one at 24 iterations; "final_round"): its tail kernel takes
-    // whatever is left, however many, and runs it to termination — no lane chunk, no further
-    // round is enqueued behind it.  Every round after the one whose tail ran used to be three or
-    // four empty launches (14-19 us each round; 65536 problems of the bench workload: the rounds at
-    // 24, 48 and 96 iterations).  What survives 24 iterations are the long accept / reject chains
-    // the speculative kernel is built for, and their iteration counts spread over 25 ... 150: a
-    // lane chunk would idle on its slowest lane.
-    const int final_round = (!spec_tail || wave_tail <= 0) ? 0
-        : (h->opt_final_round >= 0 ? h->opt_final_round : kFinalRound);
-    while (done < max_iter) {
-      int32_t* const count = cv.count + round;
-      if (!fused)
-        hipLaunchKernelGGL((k_lane_compact<T, TILED>), dim3(cgrid), dim3(256), 0, s, n, m, N, src,
-                           src_user ? 1 : 0, count_in, cv.set[cur], count, usr, c.trap);
-      const LaneSet<T>& w = cv.set[cur];
-      // the tail kernel runs from 4 iterations on; a final round reached before that is not the
-      // last (its survivors would be left in the work set, unscattered): a later round takes them
-      const bool tail_ran = wave_tail > 0 && done >= 4;
-      const bool last_round = final_round > 0 && round + 1 >= final_round && tail_ran;
-      if (tail_ran) {
-        using WL = Launch<T, Sys>;
-        const size_t lds_f = WL::fstep_lds_bytes(N);
-        IterArgs<T> t = iter_args<T>(B, max_iter, 1, w.X, w.U, w.x_term, w.lamb, w.obs, w.cost, w.K,
-                                     w.k, w.iters, w.status);
-        t.count = count; t.count_max = last_round ? (int)B : wave_tail; t.max_total = max_iter;
-        t.set_stride = B;
-        if (spec_tail) {
-          // the speculative tail delivers its problems to the caller's arrays itself (the
-          // scatter pass of the next compaction was 82 us for 7938 problems with gains)
-          t.orig = w.orig;
-          t.out_X = usr.X; t.out_U = usr.U; t.out_K = usr.K; t.out_k = usr.k;
-          t.out_lamb = usr.lamb; t.out_cost = usr.cost;
-          t.out_iters = usr.iters; t.out_status = usr.status;
-          t.out_B = usr.B; t.out_tiled = TILED ? 1 : 0;
-          if constexpr (m == 2 && n + m <= 8) HIP_TRY(group_spec_tail<T>(h->cfg, t, s));
-        } else if (WL::kHasFstep && lds_f <= h->geo.default_dyn_lds) {
-          if constexpr (WL::kHasFstep) {
-            with_weights(c.flags, [&](auto W) {
-              hipLaunchKernelGGL((k_iterate<T, Sys, 64, W, true, true>), dim3(wave_tail), dim3(64),
-                                 lds_f, s, c, t);
-            });
-          }
-        }
-      }
-      if (last_round && spec_tail && tail_ran) {  // the tail kernel has delivered everything
-        src_user = true;  // (nothing left to scatter)
-        break;
-      }
-      // chunk lengths after the first: one chunk of 4 (the tail's second chance), then as many
-      // iterations as are done (first chunk 10: compaction points at 10, 14, 28, 56 iterations).
-      // Once the tail has run, every further round is three empty launches (14 us), so few of
-      // them (the schedule 8, 4, 4, 8, 8, 16, 16, 32, 32, ... spent 0.19 of 2.13 ms there at 65536
-      // problems; 10, 4, 4, 10, 20, 40, 12: 85 us of 1.55 ms).  Against 4, 4, 4, 4, ... with a tail
-      // of 2048: 1.69 -> 1.35 ms at 16384 problems.
-      len = done < 12 ? step : done;
-      if (done + len > max_iter || round + 2 >= kMaxRounds) len = max_iter - done;
-      LaneArgs<T> a = a0;
-      set_io(a, len, 1, w);
-      a.K = nullptr; a.k = nullptr;  // gains of work sets go to the scratch buffer (w.K == wsK)
-      a.count = count; a.resume = 1;
-      // the chunk's exit packs its survivors into the OTHER work set (none behind the last chunk)
-      plan_exit(a, false, w.orig, done + len >= max_iter ? nullptr : &cv.set[cur ^ 1],
-                cv.count + round + 1);
-      // a batch too large for the helper-wavefront form as a whole: its survivors may not be.
-      // Both kernels are enqueued and the live count decides on the device which one runs (the
-      // other is an empty launch, ~3 us): 21000 survivors of 65536 problems iterate at 46
-      // instead of 67 us per iteration.  The pair's chunk takes the options of a launch of its
-      // size (no state checkpoints, no merge, no re-rolling forward pass: all bit-identical).
-      LaneArgs<T> ap = a;
-      ap.ckpt = 0;
-      ap.merge = h->opt_merge >= 0 ? h->opt_merge : 0;
-      ap.reroll = h->opt_reroll >= 0 ? h->opt_reroll : 0;
-      const unsigned pair_max = pair_max_grid(h->geo);
-      if (pair_built(c, ap, h->opt_pair) && h->opt_pair < 0 && grid(B) > pair_max) {
-        ap.count_hi = 64 * (int)pair_max;
-        launch_pair<false>(h->geo, c, ap, pair_max, s);
-        a.count_lo = ap.count_hi;
-        launch_iterate<false>(h->geo, c, a, B, s, 0);
-      } else {
-        launch_iterate<false>(h->geo, c, a, B, s, h->opt_pair);
-      }
-      done += len;
-      src = w;
-      src_user = false;
-      count_in = count;
-      cur ^= 1;
-      round++;
-    }
-    // every remaining problem has a terminal status now: scatter them all
-    if (!fused && !src_user) {
-      LaneSet<T> none;
-      std::memset(&none, 0, sizeof(none));
-      hipLaunchKernelGGL((k_lane_compact<T, TILED>), dim3(cgrid), dim3(256), 0, s, n, m, N, src, 0,
-                         count_in, none, cv.count + round, usr, c.trap);
-    }
-    HIP_TRY(hipGetLastError());
-    return I2LQR_OK;
-  }
-
-  static int iterate(i2lqr_handle* h, int64_t B, int n_iters, int early_exit, void* X, void* U,
-                     const void* x_term, void* lamb, const void* obs, void* cost, void* K, void* k,
-                     int32_t* iters, int32_t* status, hipStream_t s) {
-    if (early_exit && n_iters == h->cfg.max_iter && chunked(h, B))
-      return solve_compacting(h, B, X, U, x_term, lamb, obs, cost, K, k, iters, status, s);
-    if (int rc = need_ws(h, B)) return rc;
-    const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    LaneArgs<T> a;
-    carve(h, B, a);
-    set_io(a, n_iters, early_exit, user_set(B, X, U, x_term, lamb, obs, cost, K, k, iters, status));
-    a.max_total = n_iters;
-    if (early_exit) {  // solve() is bound by its slowest problem's latency, not by HBM traffic
-      if (h->opt_reroll < 0) a.reroll = 0;
-      if (h->opt_defer < 0) a.defer = 0;
-      finish_options(h, B, a);
-    }
-    launch_iterate<TILED>(h->geo, c, a, B, s, h->opt_pair);
-    HIP_TRY(hipGetLastError());
-    return I2LQR_OK;
-  }
-  // 1 if the (first) launch of i2lqr_iterate / i2lqr_solve for B problems is the helper-wavefront
-  // kernel: the SAME carve + option + use_pair sequence the launchers above run, on scratch
-  // arguments (no launch, no device access) — i2lqr_iterate_kernel / i2lqr_solve_kernel (ADVICE r5:
-  // a hand-written mirror of these conditions had drifted).
-  static int solve_chained(i2lqr_handle*, int64_t, int, void*, void*, const void*, void*, const void*,
-                           void*, void*, void*, int32_t*, int32_t*, hipStream_t) {
-    return fail(I2LQR_ERR_UNSUPPORTED, "chains are problem-major batches (the controller's path)");
-  }
-  static int names_pair(i2lqr_handle* h, int64_t B, int early_exit) {
-    const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    LaneArgs<T> a;
-    carve(h, B, a);
-    if (early_exit && !chunked(h, B)) {  // (the single-launch solve: iterate() above)
-      if (h->opt_reroll < 0) a.reroll = 0;
-      if (h->opt_defer < 0) a.defer = 0;
-      finish_options(h, B, a);
-    }
-    return use_pair(h->geo, c, a, B, h->opt_pair) ? 1 : 0;
-  }
-  static int rollout(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term, void* cost,
-                     hipStream_t s) {
-    if (int rc = need_ws(h, B)) return rc;
-    const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    LaneArgs<T> a;
-    carve(h, B, a);
-    with_weights<kStageWeights>(c.flags, [&](auto W) {
-      hipLaunchKernelGGL((k_lane_rollout<T, Sys, W, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
-                         (T*)X, (T*)U, (const T*)x_term, (T*)cost);
-    });
-    HIP_TRY(hipGetLastError());
-    return I2LQR_OK;
-  }
-  static int backward(i2lqr_handle* h, int64_t B, const void* X, const void* U, const void* x_term,
-                      const void* lamb, const void* obs, void* K, void* k, hipStream_t s) {
-    if (int rc = need_ws(h, B)) return rc;
-    const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    LaneArgs<T> a;
-    carve(h, B, a);
-    with_weights<kStageWeights>(c.flags, [&](auto W) {
-      hipLaunchKernelGGL((k_lane_backward<T, Sys, W, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
-                         (const T*)X, (const T*)U, (const T*)x_term, (const T*)lamb, (const T*)obs,
-                         (T*)K, (T*)k);
-    });
-    HIP_TRY(hipGetLastError());
-    return I2LQR_OK;
-  }
-  static int forward(i2lqr_handle* h, int64_t B, const void* X, const void* U, const void* x_term,
-                     const void* K, const void* k, void* Xn, void* Un, void* cost_new,
-                     hipStream_t s) {
-    if (int rc = need_ws(h, B)) return rc;
-    const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    LaneArgs<T> a;
-    carve(h, B, a);
-    with_weights<kStageWeights>(c.flags, [&](auto W) {
-      hipLaunchKernelGGL((k_lane_forward<T, Sys, W, TILED>), dim3(grid(B)), dim3(64), 0, s, c, B,
-                         (const T*)X, (const T*)U, (const T*)x_term, (const T*)K, (const T*)k,
-                         (T*)Xn, (T*)Un, (T*)cost_new);
-    });
-    HIP_TRY(hipGetLastError());
-    return I2LQR_OK;
-  }
-};
-
 // f(L()) with L the launcher of the handle's layout, precision and plant (validated by i2lqr_create)
 template <class F> int dispatch(const i2lqr_handle* h, F&& f) {
   return visit_plant(h->cfg, [&](auto t, auto sys) {
@@ -1100,13 +480,8 @@ template <class F> int dispatch(const i2lqr_handle* h, F&& f) {
     return f(Launch<T, Sys>());
   });
 }
-int dispatch_iterate(i2lqr_handle* h, int64_t B, int n_iters, int early_exit, void* X, void* U,
-                     const void* x_term, void* lamb, const void* obs, void* cost, void* K, void* k,
-                     int32_t* iters, int32_t* status, void* stream) {
-  return dispatch(h, [&](auto L) {
-    return L.iterate(h, B, n_iters, early_exit, X, U, x_term, lamb, obs, cost, K, k, iters, status,
-                     (hipStream_t)stream);
-  });
+int dispatch_iterate(i2lqr_handle* h, const SolveIO& io, void* stream) {
+  return dispatch(h, [&](auto L) { return L.iterate(h, io, (hipStream_t)stream); });
 }
 
 // Live handles: i2lqr_destroy of NULL is a no-op, of a pointer that is not (or no longer) a live
@@ -1135,6 +510,16 @@ int check_common(const i2lqr_handle* h, int64_t B) {
   if (!h) return fail(I2LQR_ERR_INVALID, "null handle");
   if (B < 0) return fail(I2LQR_ERR_INVALID, "negative batch %lld", (long long)B);
   if (B > (int64_t)0x7fffffff) return fail(I2LQR_ERR_INVALID, "batch %lld too large", (long long)B);
+  return I2LQR_OK;
+}
+
+// The arrays a solve call cannot do without (extra_null: one of the call's own is missing), and K
+// and k as a pair
+int check_io(const SolveIO& io, bool extra_null = false) {
+  if (!io.X || !io.U || !io.x_term || !io.lamb || !io.cost || extra_null)
+    return fail(I2LQR_ERR_INVALID, "null buffer");
+  if ((io.K == nullptr) != (io.k == nullptr))
+    return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
   return I2LQR_OK;
 }
 
@@ -1465,8 +850,8 @@ int64_t i2lqr_workspace_bytes(const i2lqr_handle* h, int64_t B) {
   return visit_plant(h->cfg, [&](auto t, auto sys) {
     using T = decltype(t);
     using Sys = decltype(sys);
-    return tiled ? LaneLaunch<T, Sys, true>::ws_bytes(h->cfg.N, B)
-                 : LaneLaunch<T, Sys, false>::ws_bytes(h->cfg.N, B);
+    using L = LaneLaunch<T, Sys, false>;
+    return tiled ? LaneLaunch<T, Sys, true>::ws_bytes(L::shape(h), B) : L::ws_bytes(L::shape(h), B);
   });
 }
 
@@ -1553,7 +938,7 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch) {
   if (!h) return fail(I2LQR_ERR_INVALID, "null handle");
   if (h->cfg.layout == I2LQR_LAYOUT_PROBLEM_MAJOR && min_batch > 0)
     return fail(I2LQR_ERR_UNSUPPORTED, "compaction applies to the batch-minor / batch-tiled layouts");
-  h->compact_min_batch = min_batch < 0 ? -1 : min_batch;
+  h->lane.compact_min_batch = min_batch < 0 ? -1 : min_batch;
   return I2LQR_OK;
 }
 
@@ -1569,20 +954,21 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   if (!h || !name) return fail(I2LQR_ERR_INVALID, "null handle or option name");
   if (value < -1 || value > 0x7fffffff) return fail(I2LQR_ERR_INVALID, "option value out of range");
   const int v = (int)value;
-  if (!strcmp(name, "defer_states")) h->opt_defer = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "reroll_nominal")) h->opt_reroll = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "lds_gain_steps")) h->opt_lds_steps = v;
-  else if (!strcmp(name, "merge_inputs")) h->opt_merge = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "checkpoint_states")) h->opt_ckpt = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "stagger")) h->opt_stagger = v;
+  LaneTune& lane = h->lane;
+  if (!strcmp(name, "defer_states")) lane.opt_defer = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "reroll_nominal")) lane.opt_reroll = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "lds_gain_steps")) lane.opt_lds_steps = v;
+  else if (!strcmp(name, "merge_inputs")) lane.opt_merge = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "checkpoint_states")) lane.opt_ckpt = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "stagger")) lane.opt_stagger = v;
   else if (!strcmp(name, "per_step_jacobians")) h->opt_fstep = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "wave_tail")) h->wave_tail = v < 0 ? -1 : (v > 65536 ? 65536 : v);
-  else if (!strcmp(name, "first_chunk")) h->opt_first_chunk = v < 1 ? -1 : (v > 1024 ? 1024 : v);
-  else if (!strcmp(name, "helper_wavefront")) h->opt_pair = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "state_buffers")) h->opt_two_x = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "chunk_step")) h->opt_chunk_step = v < 1 ? -1 : (v > 1024 ? 1024 : v);
-  else if (!strcmp(name, "fused_compaction")) h->opt_fuse = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "final_round")) h->opt_final_round = v < 0 ? -1 : (v > 20 ? 20 : v);
+  else if (!strcmp(name, "wave_tail")) lane.wave_tail = v < 0 ? -1 : (v > 65536 ? 65536 : v);
+  else if (!strcmp(name, "first_chunk")) lane.opt_first_chunk = v < 1 ? -1 : (v > 1024 ? 1024 : v);
+  else if (!strcmp(name, "helper_wavefront")) lane.opt_pair = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "state_buffers")) lane.opt_two_x = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "chunk_step")) lane.opt_chunk_step = v < 1 ? -1 : (v > 1024 ? 1024 : v);
+  else if (!strcmp(name, "fused_compaction")) lane.opt_fuse = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "final_round")) lane.opt_final_round = v < 0 ? -1 : (v > 20 ? 20 : v);
   else if (!strcmp(name, "speculate")) h->opt_spec = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "group_workspace")) h->opt_group_ws = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "group_overlap")) h->opt_group_overlap = v < 0 ? -1 : (v != 0);
@@ -1666,10 +1052,8 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
   if (h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR) {
     if (h->cfg.system_id == I2LQR_SYS_QUAD12) return "k_lane_iterate_rows";
     // the helper-wavefront form (both precisions, with or without stage weights): decided by the
-    // launcher's own helpers on scratch arguments (LaneLaunch::names_pair)
-    const auto pair = [&](auto L) {
-      return L.names_pair(const_cast<i2lqr_handle*>(h), B, early_exit ? 1 : 0);
-    };
+    // launcher's own rules (LaneLaunch::names_pair)
+    const auto pair = [&](auto L) { return L.names_pair(h, B, early_exit ? 1 : 0); };
     return dispatch(h, pair) == 1 ? "k_lane_iterate_pair" : "k_lane_iterate";
   }
   switch (select_fused(h, B, early_exit, nullptr)) {
@@ -1741,11 +1125,9 @@ int i2lqr_iterate(i2lqr_handle* h, int64_t B, int32_t n_iters, void* X, void* U,
   if (int rc = check_common(h, B)) return rc;
   if (n_iters < 0) return fail(I2LQR_ERR_INVALID, "negative n_iters");
   if (B == 0) return I2LQR_OK;
-  if (!X || !U || !x_term || !lamb || !cost) return fail(I2LQR_ERR_INVALID, "null buffer");
-  if ((K == nullptr) != (k == nullptr))
-    return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
-  return debug_check(dispatch_iterate(h, B, n_iters, 0, X, U, x_term, lamb, obs, cost, K, k, iters,
-                                      status, stream), stream);
+  const SolveIO io{B, n_iters, 0, X, U, x_term, lamb, obs, cost, K, k, iters, status};
+  if (int rc = check_io(io)) return rc;
+  return debug_check(dispatch_iterate(h, io, stream), stream);
 }
 
 int i2lqr_solve(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term, void* lamb,
@@ -1753,11 +1135,9 @@ int i2lqr_solve(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term
                 void* stream) {
   if (int rc = check_common(h, B)) return rc;
   if (B == 0) return I2LQR_OK;
-  if (!X || !U || !x_term || !lamb || !cost) return fail(I2LQR_ERR_INVALID, "null buffer");
-  if ((K == nullptr) != (k == nullptr))
-    return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
-  return debug_check(dispatch_iterate(h, B, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, k,
-                                      iters, status, stream), stream);
+  const SolveIO io{B, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, k, iters, status};
+  if (int rc = check_io(io)) return rc;
+  return debug_check(dispatch_iterate(h, io, stream), stream);
 }
 
 int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void* X, void* U,
@@ -1768,16 +1148,14 @@ int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void
   if (chains * (int64_t)chain_len > (int64_t)0x7fffffff)
     return fail(I2LQR_ERR_INVALID, "%lld chains of %d problems", (long long)chains, chain_len);
   if (chains == 0) return I2LQR_OK;
-  if (!X || !U || !x_term || !lamb || !cost) return fail(I2LQR_ERR_INVALID, "null buffer");
-  if ((K == nullptr) != (k == nullptr))
-    return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
+  const SolveIO io{chains, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, k, iters, status};
+  if (int rc = check_io(io)) return rc;
   // (k_chain_box carries the models: nothing to refuse with "wave_chain" 1)
   if (const WaveForm f = h->model.form(); f != WAVE_PLAIN && h->opt_wave_chain != 1)
     return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which %s, "
                 "or solve the chain steps one after the other", wave_lack_phrase(f));
   const int rc = dispatch(h, [&](auto L) {
-    return L.solve_chained(h, chains, chain_len, X, U, x_term, lamb, obs, cost, K, k, iters, status,
-                           (hipStream_t)stream);
+    return L.solve_chained(h, io, chain_len, (hipStream_t)stream);
   });
   return debug_check(rc, stream);
 }
@@ -1859,15 +1237,12 @@ int i2lqr_iterate_pick(i2lqr_handle* h, int64_t B, int32_t n_iters, void* X, voi
   if (B == 0)  // nothing to solve; an empty pick is (-1, +inf) as in i2lqr_argmin
     return best_idx ? i2lqr_argmin(h, 0, nullptr, best_idx, best_cost, workspace, workspace_bytes,
                                    stream) : I2LQR_OK;
-  if (!X || !U || !x_term || !lamb || !cost || !qfun || !cost_it)
-    return fail(I2LQR_ERR_INVALID, "null buffer");
-  if ((K == nullptr) != (k == nullptr))
-    return fail(I2LQR_ERR_INVALID, "K and k must both be given or both be NULL");
+  const SolveIO io{B, n_iters, 0, X, U, x_term, lamb, obs, cost, K, k, iters, status};
+  if (int rc = check_io(io, !qfun || !cost_it)) return rc;
   i2lqr_handle::Epilogue epi{qfun, outer_iter, max_relax_iter, cost_it, workspace, best_idx,
                              best_cost, false};
   t_epi = &epi;
-  const int rc = dispatch_iterate(h, B, n_iters, 0, X, U, x_term, lamb, obs, cost, K, k, iters,
-                                  status, stream);
+  const int rc = dispatch_iterate(h, io, stream);
   t_epi = nullptr;
   if (rc != I2LQR_OK) return rc;
   if (!epi.fused) {  // kernel families without the epilogue: the same three steps as launches

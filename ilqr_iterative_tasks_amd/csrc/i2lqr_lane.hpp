@@ -20,6 +20,7 @@
 
 #include <type_traits>
 
+#include "i2lqr_lane_plan.hpp"
 #include "i2lqr_systems.hpp"
 #include "i2lqr_wave.hpp"
 
@@ -193,7 +194,7 @@ __device__ __forceinline__ void lane_exit_compact(const LaneCompact<T>& cp, cons
 // (bit-identical to what a full rollout stores: same code, same inputs) and reads them from
 // there.  X traffic per iteration drops from n (N+1) read + n N written to a quarter of that, for
 // one more plant step per horizon step; the caller's X is completed by one full re-roll at exit.
-constexpr int kSeg = 4;
+// (kSeg = 4: i2lqr_lane_plan.hpp, where the launcher budgets the segment's LDS)
 
 // Barrier of a main / helper pair of wavefronts (k_lane_iterate_pair) that orders their LDS traffic
 // ONLY.  __syncthreads() is a workgroup-scope release + acquire on every address space: its

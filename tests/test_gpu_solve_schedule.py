@@ -1,5 +1,6 @@
-"""The schedule space of the chunked, compacting solve (solve_compacting in csrc/i2lqr_abi.hip) on
-the lane layouts: a first chunk in place, compaction rounds folded into the chunks' exit (or as
+"""The schedule space of the chunked, compacting solve (solve_compacting in
+csrc/i2lqr_lane_launch.hpp, its rounds from chunk_schedule in csrc/i2lqr_lane_plan.hpp) on the lane
+layouts: a first chunk in place, compaction rounds folded into the chunks' exit (or as
 launches of their own), a tail kernel gated on the live count, a final round whose tail takes every
 survivor, and a helper-wavefront or plain kernel per later chunk.  Six public options reshape it
 ("first_chunk", "chunk_step", "final_round", "wave_tail", "fused_compaction", "speculate"), a

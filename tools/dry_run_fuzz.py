@@ -28,8 +28,9 @@ ap.add_argument("--configs", type=int, default=1000)
 ap.add_argument("--seed", type=int, default=20260406)
 ap.add_argument("--verbose", action="store_true")
 ap.add_argument("--trace", metavar="FILE",
-                help="write every launch record (instantiation, shape, arguments) to FILE: two builds "
-                     "of the library that enqueue the same launches write identical files")
+                help="write every launch record (instantiation, shape, arguments), every refusal's "
+                     "text and the kernels every handle reports to FILE: two builds of the library "
+                     "that enqueue the same launches and say the same write identical files")
 args = ap.parse_args()
 
 lib = _abi.load_library()
@@ -65,6 +66,12 @@ class Arena:
 
 
 trace = open(args.trace, "w") if args.trace else None
+
+
+def note(line):
+    """A line of the trace that is no launch: a refusal's text, the kernels a handle reports."""
+    if trace:
+        trace.write(f"# {line}\n")
 
 
 def report(label=""):
@@ -236,6 +243,7 @@ for it in range(args.configs):
     stats["configs"] += 1
     if rc != 0:
         stats["refused"] += 1
+        note(f"configuration {it} create rc {rc}: {lib.i2lqr_last_error().decode()}")
         continue
     n_obs = 1  # records per problem: obs[B][n_obs][6] once "obstacles" is accepted
     for name in rng.choice(list(OPTIONS), size=int(rng.integers(0, 5)), replace=False):
@@ -319,7 +327,8 @@ for it in range(args.configs):
         rc = calls[ci]()
         stats["calls"] += 1
         stats["ok" if rc == 0 else "refused"] += 1
-        bad, text = report(f"configuration {it} call {ci} rc {rc}")
+        why = "" if rc == 0 else ": " + lib.i2lqr_last_error().decode()  # (the refusal's text)
+        bad, text = report(f"configuration {it} call {ci} rc {rc}{why}")
         if bad:
             print(f"VIOLATION in configuration {it}: {system} N={N} {dtype} layout={layout} B={B} "
                   f"call {ci} rc={rc}\n{text}")
@@ -333,7 +342,9 @@ for it in range(args.configs):
         stats["launches"] += text.count("\n")
         if args.verbose:
             print(it, system, N, dtype, layout, B, "call", ci, "rc", rc, lib.i2lqr_last_error().decode()[:80])
-    assert lib.i2lqr_iterate_kernel(h, B) is not None and lib.i2lqr_solve_kernel(h, B) is not None
+    names = lib.i2lqr_iterate_kernel(h, B), lib.i2lqr_solve_kernel(h, B)
+    assert None not in names
+    note(f"configuration {it} iterate on {names[0].decode()}, solve on {names[1].decode()}")
     assert lib.i2lqr_destroy(h) == 0
 if trace:
     trace.close()
