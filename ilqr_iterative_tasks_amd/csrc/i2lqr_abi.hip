@@ -28,6 +28,8 @@
 // LaneLaunch; brings in i2lqr_dryrun.hpp, whose macros record every launch below as well (empty
 // unless -DI2LQR_DRY_RUN: the ASan build)
 #include "i2lqr_lane_launch.hpp"
+// Launch (behind it: its launches are recorded too)
+#include "i2lqr_column_launch.hpp"
 
 using namespace i2lqr;
 
@@ -149,326 +151,6 @@ int debug_check(int rc, void* stream) {
 }  // namespace
 
 namespace {
-thread_local i2lqr_handle::Epilogue* t_epi = nullptr;  // (struct i2lqr_handle: i2lqr_handle.hpp)
-}
-
-namespace {
-
-// Which fused kernel a problem-major call runs on: ONE function, used by the launchers and by
-// i2lqr_iterate_kernel / i2lqr_solve_kernel (what bench.py labels its results with).
-enum FusedKernel { K_WAVE, K_WAVE_OPT, K_GROUP, K_GROUP16, K_GROUP_WS, K_SPEC, K_SPEC16, K_QUAD, K_INVALID };
-// (measured on the 256-CU chip; DeviceGeometry::scaled() elsewhere)
-constexpr int64_t kAutoGroupBatch = 1024;  // eight-lane kernel from here (automatic)
-constexpr int64_t kAutoSpecBatch = 12288;  // speculative form for solves up to here (automatic)
-
-// *why: the message of K_INVALID (a forced option the configuration cannot honour)
-FusedKernel select_fused(const i2lqr_handle* h, int64_t B, bool early_exit, const char** why) {
-  static const char* none = "";
-  if (!why) why = &none;
-  // a model is on ("line_search", "obstacles", a state box): every call runs on that form of the
-  // one-problem-per-wavefront kernel (i2lqr_wave_opt.h), whatever the batch size
-  if (const WaveForm f = h->model.form(); f != WAVE_PLAIN) {
-    if (h->opt_group == 8 || h->opt_group == 16) {
-      static thread_local char msg[128];
-      snprintf(msg, sizeof(msg), "%s runs on the one-problem-per-wavefront kernel: not together "
-               "with \"group_lanes\" = 8 or 16", wave_phrase(f));
-      *why = msg;
-      return K_INVALID;
-    }
-    return K_WAVE_OPT;
-  }
-  const bool m2 = h->cfg.m == 2 && h->cfg.n + h->cfg.m <= 8;
-  const bool q16 = h->cfg.n + h->cfg.m == 16;
-  if (m2) {
-    // Eight lanes per problem, eight problems per wavefront (i2lqr_group.hpp).  Automatic where it
-    // is built (the bicycles, Q = R = 0) from 1024 problems: below that every problem gets a SIMD
-    // of its own either way and the one-problem-per-wavefront kernel's iteration is ~8 % shorter
-    // (tools/group_ab.py: 0.195 vs 0.212 ms per 10 iterations at 64-256 problems, 0.219 vs 0.213
-    // at 1024, 0.63 vs 0.25 at 4096).
-    const bool can = group_supported(h->cfg);
-    if (h->opt_group == 8 && !can) {
-      *why = "\"group_lanes\" = 8 needs a bicycle plant with Q = R = 0 and a horizon whose eight "
-             "problem slices fit a CU's LDS";
-      return K_INVALID;
-    }
-    // Speculative form (k_group_spec): two or three wavefronts per eight problems run the
-    // iterations that follow 0, 1, (2) rejects at once; bit-identical results.  With a FIXED
-    // iteration count it measures slower than the plain kernel (0.275 vs 0.215 ms per 10
-    // iterations at 1024 problems), so it stays opt-in there.  Automatic for solves to
-    // termination (early_exit) of at most kAutoSpecBatch problems: the launch lasts as long as
-    // its slowest problem, and the slowest problems alternate accepts and rejects — i2lqr_solve
-    // 0.60 -> 0.44 ms at 16 problems, 1.21 -> 0.71 ms at 1024, 1.23 -> 1.17 at 8192.
-    // (sixteen lanes per problem — the DPP passes, four problems per workgroup — wherever its
-    // buffers fit; "group_lanes" 8 pins the eight-lane form)
-    const bool can_spec16 = group_spec_supported(h->cfg, 16), can_spec8 = group_spec_supported(h->cfg, 8);
-    const bool spec16 = h->opt_group == 16 || (h->opt_group < 0 && can_spec16);
-    const bool can_spec = spec16 ? can_spec16 : can_spec8;
-    if (h->opt_spec == 1 && !can_spec) {
-      *why = "\"speculate\" = 1 needs the eight- / sixteen-lane kernel and a horizon whose speculative "
-             "buffers fit a CU's LDS";
-      return K_INVALID;
-    }
-    if (can_spec && h->opt_group != 64 &&
-        (h->opt_spec == 1 ||
-         (h->opt_spec < 0 && h->opt_group < 0 && early_exit && B <= h->geo.scaled(kAutoSpecBatch))))
-      return spec16 ? K_SPEC16 : K_SPEC;
-    // Sixteen lanes per problem (one problem per DPP row; GroupWorker::backward_row / forward_row):
-    // no LDS round trip in the serial chains.  Four problems per wavefront: automatic for every
-    // batch that still leaves each wavefront a SIMD of its own (up to kGroup16Batch problems) —
-    // its iteration is shorter than the one-problem-per-wavefront kernel's at ANY size (0.145
-    // against 0.188 ms per 10 iterations from 1 to 512 problems, n = 6, N = 20; tools/_diag);
-    // "group_lanes" 16 / 8 / 64 pins the choice.
-    const bool can16 = group16_supported(h->cfg);  // (four slices: longer horizons than `can`)
-    if (h->opt_group == 16 && !can16) {
-      *why = "\"group_lanes\" = 16 needs a bicycle plant with Q = R = 0 and a horizon whose four "
-             "problem slices fit a CU's LDS";
-      return K_INVALID;
-    }
-    // Beyond one round of 1024 wavefronts the sixteen-lane kernel runs in rounds (0.168 ms per 4096
-    // problems); the eight-lane workspace form (four wavefronts of eight problems per CU) is the
-    // better choice only between 4096 and kGroupWsTop problems — and only with the caller's
-    // workspace registered.
-    const int64_t need = can ? group_workspace_bytes(h->cfg, B) : 0;
-    const bool have_ws = need > 0 && h->ws && h->ws_bytes >= need;
-    const bool ws_range = B > h->geo.scaled(kGroupWsBatch) && B <= h->geo.scaled(group_ws_top(h->cfg));
-    if (h->opt_group == 16 ||
-        (h->opt_group < 0 && can16 && h->opt_group_ws != 1 && !(ws_range && can && have_ws)))
-      return K_GROUP16;
-    if (h->opt_group == 8 || (h->opt_group < 0 && can && B >= h->geo.scaled(kAutoGroupBatch))) {
-      // "group_workspace" 0 / 1 pins the choice of the eight-lane form
-      if (h->opt_group_ws == 1 && !have_ws) {
-        *why = "\"group_workspace\" = 1 needs a registered workspace of i2lqr_workspace_bytes() "
-               "for this batch";
-        return K_INVALID;
-      }
-      if (have_ws && (h->opt_group_ws == 1 ||
-                      (h->opt_group_ws < 0 && (ws_range || (h->opt_group == 8 && B > h->geo.scaled(kGroupWsBatch))))))
-        return K_GROUP_WS;
-      return K_GROUP;
-    }
-  } else if (h->opt_group == 8) {
-    *why = "\"group_lanes\" = 8 is built for the m = 2 plants only";
-    return K_INVALID;
-  }
-  if (q16) {
-    // Sixteen lanes per problem, four problems per wavefront (i2lqr_quad.hpp): needs the caller's
-    // workspace (i2lqr_workspace_bytes); automatic whenever it is registered.
-    const bool can = quad_supported(h->cfg);
-    const bool have_ws = h->ws && h->ws_bytes >= quad_workspace_bytes(h->cfg, B);
-    if (h->opt_group == 16 && !(can && have_ws)) {
-      *why = "\"group_lanes\" = 16 needs Q = R = 0 and a registered workspace of "
-             "i2lqr_workspace_bytes() for this batch";
-      return K_INVALID;
-    }
-    if ((h->opt_group == 16 || h->opt_group < 0) && can && have_ws) return K_QUAD;
-  } else if (h->opt_group == 16 && !m2) {
-    *why = "\"group_lanes\" = 16 is built for the bicycles (DPP row form) and the n + m = 16 plant";
-    return K_INVALID;
-  }
-  return K_WAVE;
-}
-
-// The opt-in form of a call (chained: k_chain_box) takes its records and the box's words behind the
-// handle's slice: I2LQR_OK if the sum fits the device's dynamic LDS, else the refusal with the bytes.
-int wave_lds_check(const i2lqr_handle* h, int n, size_t word, bool chained) {
-  const WaveForm f = h->model.form(chained);
-  const size_t need = h->lds_bytes + h->model.extra_lds_bytes(f, n, h->cfg.N, word);
-  if (need <= h->geo.max_dyn_lds) return I2LQR_OK;
-  const int n_obs = h->model.records();
-  char with[64];
-  if (f == WAVE_OBS)
-    snprintf(with, sizeof(with), "\"obstacles\" = %d", n_obs);
-  else
-    snprintf(with, sizeof(with), "%s and %d obstacle record%s",
-             chained ? "\"wave_chain\"" : wave_phrase(f), n_obs, n_obs > 1 ? "s" : "");
-  return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d with %s needs %zu B of LDS per wavefront (> %zu KiB)",
-              h->cfg.N, with, need, h->geo.max_dyn_lds / 1024);
-}
-
-// One launcher per (dtype, system); LANES fixed at 64 = one problem per wavefront.
-template <class T, class Sys> struct Launch {
-  static constexpr int n = Sys::n, m = Sys::m, LANES = 64;
-  using Cfg = DevCfg<T, n, m>;
-
-  static size_t lds_bytes(int N) { return (size_t)Layout<Sys>(N).total * sizeof(T) * (64 / LANES); }
-  static size_t fstep_lds_bytes(int N) { return wave_fstep_lds_bytes<T, Sys>(N); }
-  static constexpr bool kHasFstep = kWaveHasFstep<Sys>;
-  static unsigned grid(int64_t B) { return (unsigned)((B + (64 / LANES) - 1) / (64 / LANES)); }
-
-  static int prepare(i2lqr_handle* h) {
-    h->lanes = LANES;
-    h->lds_bytes = lds_bytes(h->cfg.N);
-    if (h->lds_bytes > h->geo.max_dyn_lds)
-      return fail(I2LQR_ERR_UNSUPPORTED, "horizon %d needs %zu B of LDS per wavefront (> %zu KiB)",
-                  h->cfg.N, h->lds_bytes, h->geo.max_dyn_lds / 1024);
-    if (h->lds_bytes > h->geo.default_dyn_lds)
-      for (const void* kernel :
-           {(const void*)k_iterate<T, Sys, LANES, false>, (const void*)k_iterate<T, Sys, LANES, true>,
-            (const void*)k_backward<T, Sys, LANES, false>, (const void*)k_backward<T, Sys, LANES, true>,
-            (const void*)k_forward<T, Sys, LANES, false>, (const void*)k_forward<T, Sys, LANES, true>,
-            (const void*)k_rollout<T, Sys, LANES, false>, (const void*)k_rollout<T, Sys, LANES, true>})
-        HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)h->lds_bytes));
-    return I2LQR_OK;
-  }
-
-  static int iterate(i2lqr_handle* h, const SolveIO& io, hipStream_t s) {
-    const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    const int64_t B = io.B;
-    IterArgs<T> a = iter_args<T>(io);
-#ifdef I2LQR_STAMPS
-    a.dbg = (unsigned long long*)h->ws;  // diagnostic build: caller registers [B][8] u64 here
-#endif
-    const char* why = "";
-    const FusedKernel fk = select_fused(h, B, io.early_exit != 0, &why);
-    if (t_epi && (fk == K_GROUP || fk == K_GROUP16 || fk == K_GROUP_WS)) {  // the eight-lane kernels carry the epilogue
-      a.qfun = t_epi->qfun;
-      a.outer_iter = t_epi->outer_iter;
-      a.max_relax_iter = t_epi->max_relax_iter;
-      a.cost_it = (T*)t_epi->cost_it;
-      if (t_epi->best_idx) {
-        a.pick_part = (MinPair<T>*)t_epi->part;
-        a.pick_ticket = h->ticket + h->ticket_next.fetch_add(1, std::memory_order_relaxed) %
-                                        i2lqr_handle::kTickets;
-        a.best_idx = t_epi->best_idx;
-        a.best_cost = (T*)t_epi->best_cost;
-      }
-      t_epi->fused = true;
-    }
-    switch (fk) {
-      case K_INVALID:
-        return fail(I2LQR_ERR_UNSUPPORTED, "%s", why);
-      case K_SPEC:
-      case K_SPEC16:
-        if constexpr (m == 2 && n + m <= 8) {
-          HIP_TRY(group_spec_iterate<T>(h->cfg, a, s, fk == K_SPEC16 ? 16 : 8));
-          return I2LQR_OK;
-        }
-        break;
-      case K_GROUP:
-        if constexpr (m == 2 && n + m <= 8) {
-          HIP_TRY(group_iterate<T>(h->cfg, a, s));
-          return I2LQR_OK;
-        }
-        break;
-      case K_GROUP16:
-        if constexpr (m == 2 && n + m <= 8) {
-          HIP_TRY(group16_iterate<T>(h->cfg, a, s, h->opt_group_overlap != 0,
-                                     h->opt_group_fixed != 0));
-          return I2LQR_OK;
-        }
-        break;
-      case K_GROUP_WS:
-        if constexpr (m == 2 && n + m <= 8) {
-          HIP_TRY(group_iterate_ws<T>(h->cfg, a, h->ws, s));
-          return I2LQR_OK;
-        }
-        break;
-      case K_QUAD:
-        if constexpr (n + m == 16) {
-          HIP_TRY(quad_iterate<T>(h->cfg, a, h->ws, s));
-          return I2LQR_OK;
-        }
-        break;
-      case K_WAVE_OPT:
-        if (int rc = wave_lds_check(h, n, sizeof(T), false)) return rc;
-        HIP_TRY(wave_opt_launch<T>(h->cfg, a, h->model, false, h->lds_bytes, s));
-        return I2LQR_OK;
-      case K_WAVE:
-        break;
-    }
-    // Per-step F matrices (prep() writes them in parallel over t; the serial recursion then has no
-    // Jacobian refresh) double the LDS slice: taken when every wavefront of the launch still fits
-    // on the chip at once, i.e. in the latency-bound regime this variant exists for.
-    const size_t lds_f = fstep_lds_bytes(h->cfg.N);
-    const int64_t waves_per_cu = (grid(B) + h->geo.cus - 1) / h->geo.cus;
-    const bool fstep = kHasFstep && lds_f <= h->geo.default_dyn_lds &&
-                       (h->opt_fstep >= 0 ? h->opt_fstep != 0
-                                          : waves_per_cu * lds_f <= h->geo.lds_per_cu - 10 * 1024);
-    if constexpr (kHasFstep) {
-      if (fstep) {
-        with_weights(c.flags, [&](auto W) {
-          hipLaunchKernelGGL((k_iterate<T, Sys, LANES, W, true>), dim3(grid(B)), dim3(64), lds_f, s, c, a);
-        });
-        HIP_TRY(hipGetLastError());
-        return I2LQR_OK;
-      }
-    }
-    with_weights(c.flags, [&](auto W) {
-      hipLaunchKernelGGL((k_iterate<T, Sys, LANES, W>), dim3(grid(B)), dim3(64), h->lds_bytes, s, c, a);
-    });
-    HIP_TRY(hipGetLastError());
-    return I2LQR_OK;
-  }
-  static int names_pair(const i2lqr_handle*, int64_t, int) { return 0; }
-  // io.B chains of k problems each in ONE launch: k_group_spec<.., CHAIN> where it is built for the
-  // handle; otherwise, and with a model on, "wave_chain" 1 runs k_chain_box (i2lqr_wave_chain.hip)
-  // with the handle's state box, "obstacles" and "line_search"
-  static int solve_chained(i2lqr_handle* h, const SolveIO& io, int k, hipStream_t s) {
-    const int64_t L = io.B;
-    constexpr bool bicycle = m == 2 && n + m <= 8;
-    const bool wc = h->opt_wave_chain == 1, model = h->model.form() != WAVE_PLAIN;
-    bool spec = false;  // (not asked about where "wave_chain" takes the model anyway)
-    if constexpr (bicycle)
-      spec = !(wc && model) && !(h->opt_spec == 0 || h->opt_group == 8 || h->opt_group == 64 ||
-                                 !group_spec_chain_supported(h->cfg, L));
-    const bool wave = wc && (model || !spec);
-    if (!wave && !spec) {
-      if (!bicycle) return fail(I2LQR_ERR_UNSUPPORTED, "chains are built for the m = 2 plants");
-      return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel: a "
-                  "bicycle plant with Q = R = 0, at most %lld chains, a horizon whose three-wavefront "
-                  "buffers fit a CU's LDS (solve the chain steps one after the other instead)",
-                  (long long)h->geo.scaled(512));
-    }
-    if (wave) {
-      const char* why = "";  // a model with "group_lanes" 8 or 16: refused as i2lqr_solve refuses it
-      if (model && select_fused(h, L, true, &why) == K_INVALID)
-        return fail(I2LQR_ERR_UNSUPPORTED, "%s", why);
-      if (int rc = wave_lds_check(h, n, sizeof(T), true)) return rc;
-    }
-    IterArgs<T> a = iter_args<T>(io);
-    a.chain_len = k;
-    if (wave) {
-      HIP_TRY(wave_opt_launch<T>(h->cfg, a, h->model, true, h->lds_bytes, s));
-    } else if constexpr (bicycle) {
-      HIP_TRY(group_spec_chain<T>(h->cfg, a, s));
-    }
-    return I2LQR_OK;
-  }
-  static int rollout(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term, void* cost,
-                     hipStream_t s) {
-    const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    with_weights(c.flags, [&](auto W) {
-      hipLaunchKernelGGL((k_rollout<T, Sys, LANES, W>), dim3(grid(B)), dim3(64), h->lds_bytes, s, c,
-                         B, (T*)X, (T*)U, (const T*)x_term, (T*)cost);
-    });
-    HIP_TRY(hipGetLastError());
-    return I2LQR_OK;
-  }
-  static int backward(i2lqr_handle* h, int64_t B, const void* X, const void* U, const void* x_term,
-                      const void* lamb, const void* obs, void* K, void* k, hipStream_t s) {
-    const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    with_weights(c.flags, [&](auto W) {
-      hipLaunchKernelGGL((k_backward<T, Sys, LANES, W>), dim3(grid(B)), dim3(64), h->lds_bytes, s, c,
-                         B, (const T*)X, (const T*)U, (const T*)x_term, (const T*)lamb,
-                         (const T*)obs, (T*)K, (T*)k);
-    });
-    HIP_TRY(hipGetLastError());
-    return I2LQR_OK;
-  }
-  static int forward(i2lqr_handle* h, int64_t B, const void* X, const void* U, const void* x_term,
-                     const void* K, const void* k, void* Xn, void* Un, void* cost_new,
-                     hipStream_t s) {
-    const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
-    with_weights(c.flags, [&](auto W) {
-      hipLaunchKernelGGL((k_forward<T, Sys, LANES, W>), dim3(grid(B)), dim3(64), h->lds_bytes, s, c,
-                         B, (const T*)X, (const T*)U, (const T*)x_term, (const T*)K, (const T*)k,
-                         (T*)Xn, (T*)Un, (T*)cost_new);
-    });
-    HIP_TRY(hipGetLastError());
-    return I2LQR_OK;
-  }
-};
 
 // f(L()) with L the launcher of the handle's layout, precision and plant (validated by i2lqr_create)
 template <class F> int dispatch(const i2lqr_handle* h, F&& f) {
@@ -490,20 +172,6 @@ std::mutex g_live_mu;
 std::unordered_set<const i2lqr_handle*>& live_handles() {
   static std::unordered_set<const i2lqr_handle*> set;
   return set;
-}
-
-// What the one-problem-per-lane kernels need of the weights (they store only the upper triangles
-// of the value function): nullptr, or what is not symmetric
-const char* lane_asymmetry(const i2lqr_config& cfg) {
-  for (int i = 0; i < cfg.n; i++)
-    for (int j = 0; j < i; j++)
-      if (cfg.Q[i * I2LQR_MAX_N + j] != cfg.Q[j * I2LQR_MAX_N + i] ||
-          cfg.Qt[i * I2LQR_MAX_N + j] != cfg.Qt[j * I2LQR_MAX_N + i])
-        return "symmetric Q and Qterminal";
-  for (int a = 0; a < cfg.m; a++)
-    for (int b = 0; b < a; b++)
-      if (cfg.R[a * I2LQR_MAX_M + b] != cfg.R[b * I2LQR_MAX_M + a]) return "a symmetric R";
-  return nullptr;
 }
 
 int check_common(const i2lqr_handle* h, int64_t B) {
@@ -756,6 +424,9 @@ int i2lqr_create(const i2lqr_config* cfg, i2lqr_handle** out) {
   if (!h) return fail(I2LQR_ERR_LAUNCH, "out of host memory");
   h->cfg = *cfg;
   h->geo = device_geometry();  // of the current device: CU count, LDS per CU / per workgroup
+  h->fit = column_fit_config(h->cfg);  // (Layout<Sys>: Launch::prepare below)
+  column_fit_group(h->cfg, h->fit);
+  column_fit_quad(h->cfg, h->fit);
   if (h->geo.wave != 64) {
     const int w = h->geo.wave;
     delete h;
@@ -836,16 +507,8 @@ int i2lqr_destroy(i2lqr_handle* h) {
 
 int64_t i2lqr_workspace_bytes(const i2lqr_handle* h, int64_t B) {
   if (!h || B < 0) return 0;
-  if (h->cfg.layout == I2LQR_LAYOUT_PROBLEM_MAJOR) {
-    if (h->cfg.system_id == I2LQR_SYS_QUAD12) return quad_workspace_bytes(h->cfg, B);
-    // the bicycles: the workspace form of the eight-lane kernel, above kGroupWsBatch problems
-    // (or whenever it is pinned); nothing below
-    // (only in the range where that form is the automatic choice, or when it is pinned: a
-    // problem-major batch of 2^20 problems does not need 5.9 GB of scratch it would never use)
-    return ((B > h->geo.scaled(kGroupWsBatch) &&
-             (B <= h->geo.scaled(group_ws_top(h->cfg)) || h->opt_group == 8)) || h->opt_group_ws == 1)
-               ? group_workspace_bytes(h->cfg, B) : 0;
-  }
+  if (h->cfg.layout == I2LQR_LAYOUT_PROBLEM_MAJOR)
+    return column_workspace_bytes(h->geo, h->fit, h->col, B);
   const bool tiled = h->cfg.layout == I2LQR_LAYOUT_BATCH_TILED;
   return visit_plant(h->cfg, [&](auto t, auto sys) {
     using T = decltype(t);
@@ -855,83 +518,16 @@ int64_t i2lqr_workspace_bytes(const i2lqr_handle* h, int64_t B) {
   });
 }
 
-// Batch sizes from which the one-problem-per-lane layouts win over the problem-major kernels.
-// Round 4 measured ONE shape (fp64, n=6, N=20: 12289 for both entry points) and applied it to every
-// bicycle configuration; round 5 measured twelve (tools/threshold_sweep.py: both bicycles x
-// horizons 6 / 20 / 50 x fp64 / fp32, interleaved on one device, every launch on its own copy of the
-// batch; profiles/r05_threshold_sweep*.json, table in profiles/README.md).  The crossover moves
-// with the horizon and the precision by far more than 25 %: the sixteen-lane kernel holds
-// 4 x (wavefronts whose LDS slices fit a CU) x 256 problems per round — 4096 at N = 20 in fp64,
-// 1024 at N = 50 — while the lane kernels' launch floor grows only linearly with N, and a solve to
-// termination on the lane layouts is chunked (compaction) from 4096 problems only.
-// Each entry is the first batch size at which the lane layout was ahead (the last size the
-// problem-major kernels won, plus one: their time is a staircase in rounds, the lane kernels'
-// is flat).  A horizon between the measured ones takes the nearer one on a log scale.
-//   quad12 (fp64): the sixteen-lane kernel 13 M it/s at any size, k_lane_iterate_rows 25 M at
-//   8192 and 73 M at 65536.
-struct LaneFrom { int64_t iterate, solve; };
-// (re-measured with the helper-wavefront form of the lane kernel, which moved the bicycle6 N = 20
-// crossover from 12289 to 8193 in fp64 and from 16385 to 12289 in fp32: profiles/
-// r05_threshold_sweep5.json ... 9.json)
-constexpr LaneFrom kLaneFrom[2][3][2] = {
-    // bicycle4:          fp64              fp32
-    /* N ~ 6  */ {{{8193, 10241}, {8193, 10241}},
-    /* N ~ 20 */  {{8193, 4096}, {8193, 10241}},
-    /* N ~ 50 */  {{4097, 4096}, {8193, 5121}}},
-    // bicycle6
-    /* N ~ 6  */ {{{8193, 6145}, {8193, 20481}},
-    /* N ~ 20 */  {{8193, 10241}, {12289, 12289}},
-    /* N ~ 50 */  {{3073, 4096}, {8193, 5121}}},
-};
-inline LaneFrom lane_from(const i2lqr_config& cfg) {
-  const int sys = cfg.system_id == I2LQR_SYS_BICYCLE6 ? 1 : 0;
-  const int nb = cfg.N <= 10 ? 0 : (cfg.N <= 31 ? 1 : 2);  // sqrt(6 x 20) = 10.95, sqrt(20 x 50) = 31.6
-  return kLaneFrom[sys][nb][cfg.dtype == I2LQR_F64 ? 0 : 1];
-}
-// quad12 (round 5, the same sweep: profiles/r05_threshold_sweep3.json, ..4.json; round 4: 8192 for
-// everything, measured at N = 50 fp64 fixed counts only).  The problem-major side is the
-// sixteen-lane kernel with its HBM workspace (rounds of 4096 problems); solves stay there longer
-// because the lane layouts have no latency tail for this plant.  [N <= 31, N > 31][fp64, fp32]
-constexpr LaneFrom kLaneFromQuad[2][2] = {
-    /* N ~ 20 */ {{4097, 8193}, {8193, 24577}},
-    /* N ~ 50 */ {{4097, 6145}, {8193, 12289}},
-};
-// with stage weights the problem-major side is the one-problem-per-wavefront kernel: 2048 problems
-// already fill the chip's SIMDs (as for the bicycles)
-constexpr int64_t kLaneFromWeights = 2048;
-
 int i2lqr_recommended_layout(const i2lqr_config* cfg, int64_t B, int32_t early_exit) {
   if (!cfg) return fail(I2LQR_ERR_INVALID, "null config");
   if (cfg->struct_size != (int32_t)sizeof(i2lqr_config))
     return fail(I2LQR_ERR_INVALID, "config struct_size %d, library expects %zu", cfg->struct_size,
                 sizeof(i2lqr_config));
   if (B < 0) return fail(I2LQR_ERR_INVALID, "negative batch %lld", (long long)B);
-  // what the lane layouts cannot run stays problem-major: non-symmetric weights (the kernels keep
-  // the upper triangles), and for quad12 (row-block kernel) fp32 WITH stage weights
-  const bool weights = has_stage_weights(*cfg);
-  bool lane_ok = !lane_asymmetry(*cfg);
-  int64_t from;
-  switch (cfg->system_id) {
-    case I2LQR_SYS_BICYCLE4:
-    case I2LQR_SYS_BICYCLE6:
-      // with stage weights the problem-major side is the one-problem-per-wavefront kernel (the
-      // column kernels are built for Q = R = 0): 1024 problems already fill the chip's SIMDs
-      from = weights ? kLaneFromWeights
-                     : (early_exit ? lane_from(*cfg).solve : lane_from(*cfg).iterate);
-      break;
-    case I2LQR_SYS_QUAD12: {
-      const LaneFrom q = kLaneFromQuad[cfg->N <= 31 ? 0 : 1][cfg->dtype == I2LQR_F64 ? 0 : 1];
-      from = weights ? kLaneFromWeights : (early_exit ? q.solve : q.iterate);
-      if (cfg->dtype != I2LQR_F64 && weights) lane_ok = false;  // fp32: Q = R = 0 (round 5)
-      break;
-    }
-    default: return fail(I2LQR_ERR_INVALID, "unknown system_id %d", cfg->system_id);
-  }
-  // measured on the 256-CU chip; on another CU count (a partitioned device) scaled by cus / 256:
-  // both sides of the crossover are occupancy effects (i2lqr_geometry.hpp)
-  from = device_geometry().scaled_from(from);
-  if (!lane_ok || B < from) return I2LQR_LAYOUT_PROBLEM_MAJOR;
-  return B % 64 == 0 ? I2LQR_LAYOUT_BATCH_TILED : I2LQR_LAYOUT_BATCH_MINOR;
+  if (cfg->system_id != I2LQR_SYS_BICYCLE4 && cfg->system_id != I2LQR_SYS_BICYCLE6 &&
+      cfg->system_id != I2LQR_SYS_QUAD12)
+    return fail(I2LQR_ERR_INVALID, "unknown system_id %d", cfg->system_id);
+  return recommended_layout(device_geometry(), *cfg, has_stage_weights(*cfg), B, early_exit != 0);
 }
 
 int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch) {
@@ -955,13 +551,14 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   if (value < -1 || value > 0x7fffffff) return fail(I2LQR_ERR_INVALID, "option value out of range");
   const int v = (int)value;
   LaneTune& lane = h->lane;
+  ColumnTune& col = h->col;
   if (!strcmp(name, "defer_states")) lane.opt_defer = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "reroll_nominal")) lane.opt_reroll = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "lds_gain_steps")) lane.opt_lds_steps = v;
   else if (!strcmp(name, "merge_inputs")) lane.opt_merge = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "checkpoint_states")) lane.opt_ckpt = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "stagger")) lane.opt_stagger = v;
-  else if (!strcmp(name, "per_step_jacobians")) h->opt_fstep = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "per_step_jacobians")) col.opt_fstep = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "wave_tail")) lane.wave_tail = v < 0 ? -1 : (v > 65536 ? 65536 : v);
   else if (!strcmp(name, "first_chunk")) lane.opt_first_chunk = v < 1 ? -1 : (v > 1024 ? 1024 : v);
   else if (!strcmp(name, "helper_wavefront")) lane.opt_pair = v < 0 ? -1 : (v != 0);
@@ -969,10 +566,10 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   else if (!strcmp(name, "chunk_step")) lane.opt_chunk_step = v < 1 ? -1 : (v > 1024 ? 1024 : v);
   else if (!strcmp(name, "fused_compaction")) lane.opt_fuse = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "final_round")) lane.opt_final_round = v < 0 ? -1 : (v > 20 ? 20 : v);
-  else if (!strcmp(name, "speculate")) h->opt_spec = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "group_workspace")) h->opt_group_ws = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "group_overlap")) h->opt_group_overlap = v < 0 ? -1 : (v != 0);
-  else if (!strcmp(name, "group_fixed_horizon")) h->opt_group_fixed = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "speculate")) col.opt_spec = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "group_workspace")) col.opt_group_ws = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "group_overlap")) col.opt_group_overlap = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "group_fixed_horizon")) col.opt_group_fixed = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "debug_self_test")) {
     // Debug build only: provoke one index violation on purpose (a Slice of 8 words indexed at 8)
     // and return what the next call would: I2LQR_ERR_LAUNCH with the decoded record.
@@ -1006,12 +603,12 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
     if (v != -1 && v != 0 && v != 1)
       return fail(I2LQR_ERR_INVALID, "\"wave_chain\" is 1 (on), or -1 / 0 (off)");
     if (v == 1 && !problem_major(h)) return refuse_layout("\"wave_chain\"");
-    h->opt_wave_chain = v == 1 ? 1 : 0;
+    col.opt_wave_chain = v == 1 ? 1 : 0;
   }
   else if (!strcmp(name, "group_lanes")) {
     if (v != -1 && v != 8 && v != 16 && v != 64)
       return fail(I2LQR_ERR_INVALID, "\"group_lanes\" is 8, 16, 64 or -1");
-    h->opt_group = v;
+    col.opt_group = v;
   }
   else return fail(I2LQR_ERR_INVALID, "unknown option '%s'", name);
   return I2LQR_OK;
@@ -1056,17 +653,8 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
     const auto pair = [&](auto L) { return L.names_pair(h, B, early_exit ? 1 : 0); };
     return dispatch(h, pair) == 1 ? "k_lane_iterate_pair" : "k_lane_iterate";
   }
-  switch (select_fused(h, B, early_exit, nullptr)) {
-    case K_SPEC: return "k_group_spec";
-    case K_SPEC16: return "k_group_spec (sixteen lanes)";
-    case K_GROUP: return "k_group_iterate";
-    case K_GROUP16: return "k_group_iterate (sixteen lanes)";
-    case K_GROUP_WS: return "k_group_iterate (workspace form)";
-    case K_QUAD: return "k_quad_iterate";
-    case K_WAVE_OPT: return wave_kernel_name(h->model.form());
-    case K_WAVE: return "k_iterate";
-    default: return "unsupported";  // the launch returns I2LQR_ERR_UNSUPPORTED
-  }
+  // (a model's form of the wavefront kernel: wave_kernel_name() of it, through column_kernel_name)
+  return column_kernel_name(column_kernel(h, B, early_exit).kernel, h->model.form());
 }
 
 const char* i2lqr_iterate_kernel(const i2lqr_handle* h, int64_t B) { return kernel_name(h, B, false); }
@@ -1151,7 +739,7 @@ int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void
   const SolveIO io{chains, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, k, iters, status};
   if (int rc = check_io(io)) return rc;
   // (k_chain_box carries the models: nothing to refuse with "wave_chain" 1)
-  if (const WaveForm f = h->model.form(); f != WAVE_PLAIN && h->opt_wave_chain != 1)
+  if (const WaveForm f = h->model.form(); f != WAVE_PLAIN && h->col.opt_wave_chain != 1)
     return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which %s, "
                 "or solve the chain steps one after the other", wave_lack_phrase(f));
   const int rc = dispatch(h, [&](auto L) {

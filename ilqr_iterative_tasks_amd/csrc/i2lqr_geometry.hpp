@@ -5,7 +5,7 @@
 // logical GPU) the LDS budgets, the "a SIMD for every wavefront" limits of the helper-wavefront
 // kernels and the measured batch-size thresholds follow the logical device.
 //
-// The batch-size thresholds of the kernel choice (select_fused, i2lqr_recommended_layout, the
+// The batch-size thresholds of the kernel choice (column_kernel, i2lqr_recommended_layout, the
 // scheduling options of the lane kernels) were MEASURED on the full chip (256 CUs).  They are
 // occupancy effects — where a launch stops leaving every wavefront a SIMD of its own, where it
 // starts to fill the chip — so on a device with another CU count they are scaled by cus / 256

@@ -1,5 +1,6 @@
 // The handle behind the C-ABI (include/i2lqr.h), the argument block of a solve call and the few
-// helpers the launchers of i2lqr_abi.hip share (Launch there, LaneLaunch in i2lqr_lane_launch.hpp).
+// helpers the launchers of i2lqr_abi.hip share (Launch in i2lqr_column_launch.hpp, LaneLaunch in
+// i2lqr_lane_launch.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,7 @@
 #include <type_traits>
 
 #include "../../include/i2lqr.h"
+#include "i2lqr_column_plan.hpp"
 #include "i2lqr_geometry.hpp"
 #include "i2lqr_lane_plan.hpp"
 #include "i2lqr_wave.hpp"
@@ -15,22 +17,16 @@
 struct i2lqr_handle {
   i2lqr_config cfg;
   int lanes;        // lanes of a wavefront that cooperate on one problem (1: batch-minor layout)
-  size_t lds_bytes; // dynamic LDS per workgroup (one wavefront)
   int device;
   void* ws = nullptr;  // caller-owned scratch of the batch-minor kernels
   int64_t ws_bytes = 0;
   i2lqr::LaneTune lane;  // options of the batch-minor / batch-tiled layouts (i2lqr_lane_plan.hpp)
-  int opt_fstep = -1;  // one-problem-per-wavefront kernel: per-step Jacobian matrices in LDS; -1 = automatic
-  int opt_group = -1;  // problem-major layout: lanes per problem of the fused kernels: 8, 64; -1 = automatic
-  int opt_spec = -1;   // eight-lane kernel: speculative form (2-3 wavefronts per eight problems); -1 = automatic
-  int opt_group_ws = -1;  // eight-lane kernel: workspace form (records / gains in HBM); -1 = automatic
-  int opt_group_overlap = -1;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; -1 = automatic (on)
+  i2lqr::ColumnTune col;  // options of the problem-major layout (i2lqr_column_plan.hpp)
+  i2lqr::ColumnFit fit;   // what the kernel units know about cfg, filled in i2lqr_create
   i2lqr::WaveModel model;  // one-problem-per-wavefront kernel: "line_search", "obstacles" and the state box (i2lqr_set_state_box), all off by default (i2lqr_wave_model.hpp)
-  int opt_wave_chain = 0;  // i2lqr_solve_chained: 1 = what the speculative chain kernel is not built for runs on the one-problem-per-wavefront kernel's chained form (k_chain_box); 0: refused
-  int opt_group_fixed = -1;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; -1 = automatic (on)
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
   // it into its kernel, otherwise the call runs the separate kernels.  The pointer to the call's
-  // epilogue is THREAD-LOCAL (t_epi in i2lqr_abi.hip), not handle state: two host threads inside
+  // epilogue is THREAD-LOCAL (t_epi in i2lqr_column_launch.hpp), not handle state: two host threads inside
   // i2lqr_iterate_pick on one handle do not see each other's.
   struct Epilogue {
     const int32_t* qfun;

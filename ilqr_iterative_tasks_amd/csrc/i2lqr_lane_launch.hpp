@@ -47,7 +47,6 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
   }
   static int prepare(i2lqr_handle* h) {
     h->lanes = 1;
-    h->lds_bytes = 0;
     return I2LQR_OK;
   }
   // stage weights Q, R != 0: the bicycles in both precisions; the row-block plant (quad12) in fp64
@@ -194,7 +193,7 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     // plants, stage weights) from 2048.
     bool spec_tail = false;
     if constexpr (m == 2 && n + m <= 8)
-      spec_tail = h->opt_spec != 0 && c.flags == 0 && group_spec_tail_supported(h->cfg);
+      spec_tail = h->col.opt_spec != 0 && c.flags == 0 && group_spec_tail_supported(h->cfg);
     const int wave_tail = tune.wave_tail < 0
         ? (int)h->geo.scaled(spec_tail ? kAutoSpecTail : kAutoWaveTail) : tune.wave_tail;
     const ChunkSchedule plan = chunk_schedule(max_iter, tune.opt_first_chunk, tune.opt_chunk_step,

@@ -32,18 +32,13 @@ hipError_t quad_iterate(const i2lqr_config& cfg, const IterArgs<T>& a, void* ws,
   return hipGetLastError();
 }
 
-bool quad_supported(const i2lqr_config& cfg) {
-  if (cfg.system_id != I2LQR_SYS_QUAD12 || cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR) return false;
-  if (has_stage_weights(cfg)) return false;
-  const size_t elem = cfg.dtype == I2LQR_F64 ? 8 : 4;
-  return (size_t)QLayout<Quad12<double>>(cfg.N).lds_total * kQPW * elem <= device_geometry().max_dyn_lds;
-}
+static_assert(kQPW == kSixteenLaneProblems, "i2lqr_column_plan.hpp");
 
-int64_t quad_workspace_bytes(const i2lqr_config& cfg, int64_t B) {
-  if (!quad_supported(cfg)) return 0;
-  const int64_t Bp = (B + kQPW - 1) / kQPW * kQPW;  // whole wavefronts
-  const int64_t elem = cfg.dtype == I2LQR_F64 ? 8 : 4;
-  return Bp * (int64_t)QLayout<Quad12<double>>(cfg.N).ws_total * elem;
+void column_fit_quad(const i2lqr_config& cfg, ColumnFit& fit) {
+  if (cfg.system_id != I2LQR_SYS_QUAD12) return;
+  const QLayout<Quad12<double>> layout(cfg.N);
+  fit.lds_quad = (size_t)layout.lds_total * kQPW * (size_t)fit.word;
+  fit.ws_quad = (int64_t)layout.ws_total * fit.word;
 }
 
 template hipError_t quad_iterate<double>(const i2lqr_config&, const IterArgs<double>&, void*,

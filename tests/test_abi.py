@@ -193,9 +193,15 @@ def test_every_option_the_library_accepts_is_documented_in_the_header():
 
 def test_every_kernel_name_the_library_can_report_is_in_the_header():
     """i2lqr_iterate_kernel / i2lqr_solve_kernel return string literals of
-    csrc/i2lqr_abi.hip:kernel_name(); the header's comment is the boundary document for them."""
-    src = (ROOT / "ilqr_iterative_tasks_amd" / "csrc" / "i2lqr_abi.hip").read_text()
+    csrc/i2lqr_abi.hip:kernel_name() - the lane layouts' there, the problem-major layout's in
+    column_kernel_name() of csrc/i2lqr_column_plan.hpp; the header's comment is the boundary document
+    for them."""
+    csrc = ROOT / "ilqr_iterative_tasks_amd" / "csrc"
+    src = (csrc / "i2lqr_abi.hip").read_text()
     body = src[src.index("static const char* kernel_name("):src.index("const char* i2lqr_iterate_kernel(")]
+    assert "column_kernel_name(" in body
+    plan = (csrc / "i2lqr_column_plan.hpp").read_text()
+    body += plan[plan.index("inline const char* column_kernel_name("):plan.index("inline int64_t column_workspace_bytes(")]
     names = sorted(set(re.findall(r'"(k_[a-z_0-9]+(?: \([a-z ]+\))?|unsupported)"', body)))
     assert len(names) >= 10 and "k_lane_iterate_pair" in names, names
     hdr = re.sub(r"\s*\n \*\s*", " ", HEADER)  # the comment wraps names across lines

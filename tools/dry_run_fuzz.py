@@ -48,7 +48,8 @@ OPTIONS = {"defer_states": (0, 1), "reroll_nominal": (0, 1), "lds_gain_steps": (
            "first_chunk": (1, 4, 8, 12, 150), "helper_wavefront": (0, 1), "state_buffers": (0, 1),
            "chunk_step": (1, 2, 4, 9), "speculate": (0, 1), "group_workspace": (0, 1),
            "group_lanes": (8, 16, 64), "fused_compaction": (0, 1), "final_round": (0, 1, 2, 3, 5),
-           "line_search": (0, 2, 4, 8), "obstacles": (0, 2, 3, 8)}
+           "line_search": (0, 2, 4, 8), "obstacles": (0, 2, 3, 8), "group_overlap": (0, 1),
+           "group_fixed_horizon": (0, 1), "wave_chain": (0, 1)}
 
 
 class Arena:
@@ -222,6 +223,57 @@ for opts in ({}, {"first_chunk": 2, "final_round": 1},
 print("self-check: the chunked solve's schedules cover every survivor (automatic; final round "
       "before 4 iterations)")
 
+
+
+def column_case(system, options, B, entry, workspace=True, chain_len=1, N=20, dtype="f64"):
+    """One call on a problem-major handle, its records and words in the trace: `entry` is
+    "iterate", "solve" or "chained" (B chains of chain_len problems)."""
+    assert lib.i2lqr_dry_run(2, None, 0) == 0
+    cfg = _abi.default_config(system, N, dtype, dt=0.25, layout=0)
+    h = P()
+    assert lib.i2lqr_create(C.byref(cfg), C.byref(h)) == 0, lib.i2lqr_last_error()
+    for name, v in options.items():
+        assert lib.i2lqr_set_option(h, name.encode(), v) == 0, lib.i2lqr_last_error()
+    item, n, m, P_ = (8 if dtype == "f64" else 4), cfg.n, cfg.m, B * chain_len
+    arena = Arena()
+    X, U = arena.take(P_ * n * (N + 1) * item), arena.take(P_ * m * N * item)
+    xt, lamb, cost = arena.take(P_ * n * item), arena.take(P_ * item), arena.take(P_ * item)
+    obs = arena.take(P_ * max(options.get("obstacles", 1), 1) * 6 * item)
+    wsb = int(lib.i2lqr_workspace_bytes(h, B)) if workspace else 0
+    if wsb > 0:
+        assert lib.i2lqr_set_workspace(h, arena.take(wsb), wsb) == 0
+    tail = (X, U, xt, lamb, obs, cost, None, None, None, None, STREAM)
+    rc = {"iterate": lambda: lib.i2lqr_iterate(h, B, 5, *tail), "solve": lambda: lib.i2lqr_solve(h, B, *tail),
+          "chained": lambda: lib.i2lqr_solve_chained(h, B, chain_len, *tail)}[entry]()
+    why = "" if rc == 0 else ": " + lib.i2lqr_last_error().decode()
+    bad, text = report(f"column case {system} N={N} {dtype} {options} B={B} {entry} workspace {wsb} rc {rc}{why}")
+    assert bad == 0, text[:400]
+    note(f"iterate on {lib.i2lqr_iterate_kernel(h, B).decode()}, solve on {lib.i2lqr_solve_kernel(h, B).decode()}")
+    assert lib.i2lqr_destroy(h) == 0
+    return rc, text
+
+
+# Every kernel, wavefront count and form the problem-major launcher chooses between, once each (the
+# random configurations below reach most of them, not reliably all)
+for opts in ({}, {"group_fixed_horizon": 0}, {"group_overlap": 0}):
+    for B0 in (1024, 1025, 2048, 2049):  # sixteen-lane kernel: 3 / 2 / 1 wavefronts, both forms
+        assert column_case("bicycle6", opts, B0, "iterate")[0] == 0
+for B0, ws in ((2048, True), (2049, True), (4161, True), (4161, False)):  # eight-lane: 3 / 1, workspace form
+    assert column_case("bicycle4", {"group_lanes": 8}, B0, "iterate", workspace=ws, dtype="f32")[0] == 0
+for opts in ({}, {"group_lanes": 8, "speculate": 1}):  # speculative kernel: 3 / 2 wavefronts, sixteen and eight lanes
+    for B0 in (512, 513):
+        assert column_case("bicycle6", opts, B0, "solve")[0] == 0
+assert column_case("bicycle6", {"group_workspace": 1}, 4161, "iterate", workspace=False)[0] != 0
+for opts in ({"group_lanes": 64}, {"group_lanes": 64, "per_step_jacobians": 0}, {"line_search": 4},
+             {"line_search": 4, "group_lanes": 16}):
+    column_case("bicycle6", opts, 64, "iterate")
+for ws in (True, False):  # quad12: the sixteen-lane kernel with its workspace, else one problem per wavefront
+    assert column_case("quad12", {}, 64, "iterate", workspace=ws)[0] == 0
+for opts, B0 in (({}, 512), ({}, 513), ({"wave_chain": 1}, 513), ({"wave_chain": 1, "obstacles": 2}, 8)):
+    column_case("bicycle6", opts, B0, "chained", chain_len=2)
+assert column_case("quad12", {}, 8, "chained", chain_len=2)[0] != 0
+print("column cases: every kernel, wavefront count and chain form of the problem-major launcher recorded")
+
 stats = {"configs": 0, "calls": 0, "ok": 0, "refused": 0, "launches": 0, "schedules": 0}
 for it in range(args.configs):
     system = rng.choice(["bicycle4", "bicycle6", "quad12"], p=[0.35, 0.45, 0.2])
@@ -234,7 +286,7 @@ for it in range(args.configs):
     if rng.random() < 0.1:
         cfg.set_matrix("Q", np.eye(cfg.n) * 0.05)
     cfg.max_iter = int(rng.choice([1, 4, 8, 17, 150]))
-    B = int(rng.choice([1, 3, 64, 200, 1024, 4096, 5000, 8192, 12288, 16384, 20000, 32768, 65536, 200000]))
+    B = int(rng.choice([1, 3, 64, 200, 1024, 2048, 4096, 5000, 8192, 12288, 16384, 20000, 32768, 65536, 200000]))
     if layout == 2:
         B = max(64, B // 64 * 64)
     assert lib.i2lqr_dry_run(2, None, 0) == 0  # reset ranges and records
@@ -246,10 +298,15 @@ for it in range(args.configs):
         note(f"configuration {it} create rc {rc}: {lib.i2lqr_last_error().decode()}")
         continue
     n_obs = 1  # records per problem: obs[B][n_obs][6] once "obstacles" is accepted
+    accepted = {}
     for name in rng.choice(list(OPTIONS), size=int(rng.integers(0, 5)), replace=False):
         value = int(rng.choice(OPTIONS[name]))
-        if lib.i2lqr_set_option(h, name.encode(), value) == 0 and name == "obstacles":
-            n_obs = max(value, 1)
+        if lib.i2lqr_set_option(h, name.encode(), value) == 0:
+            accepted[str(name)] = value
+            if name == "obstacles":
+                n_obs = max(value, 1)
+    note(f"configuration {it}: {system} N={N} {dtype} layout={layout} B={B} max_iter={cfg.max_iter} "
+         f"options {accepted}")
     if rng.random() < 0.2:
         lib.i2lqr_set_compaction(h, int(rng.choice([0, 64, 4096])))
     item = 8 if dtype == "f64" else 4

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where the problem-major (latency) kernels hand over to the one-problem-per-lane (throughput)
 kernels, measured at MORE THAN ONE SHAPE: the thresholds behind
-i2lqr_recommended_layout / select_fused were measured at bicycle6 N=20 fp64 only.
+i2lqr_recommended_layout / the problem-major kernel choice were measured at bicycle6 N=20 fp64 only.
 
 For every shape x batch: the fused iterate (10 iterations, no early exit) and the solve to
 termination on (a) the problem-major layout with the library's automatic kernel choice, (b) the
