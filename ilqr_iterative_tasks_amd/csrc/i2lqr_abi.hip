@@ -570,6 +570,7 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   else if (!strcmp(name, "group_workspace")) col.opt_group_ws = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "group_overlap")) col.opt_group_overlap = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "group_fixed_horizon")) col.opt_group_fixed = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "group_chains")) col.opt_group_chains = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "debug_self_test")) {
     // Debug build only: provoke one index violation on purpose (a Slice of 8 words indexed at 8)
     // and return what the next call would: I2LQR_ERR_LAUNCH with the decoded record.

@@ -71,6 +71,7 @@ template <class T, class Sys> struct Launch {
   static int iterate(i2lqr_handle* h, const SolveIO& io, hipStream_t s) {
     const int64_t B = io.B;
     IterArgs<T> a = iter_args<T>(io);
+    a.chains = h->col.opt_group_chains != 0;
 #ifdef I2LQR_STAMPS
     a.dbg = (unsigned long long*)h->ws;  // diagnostic build: caller registers [B][8] u64 here
 #endif
@@ -165,6 +166,7 @@ template <class T, class Sys> struct Launch {
     if (plan.kind == ChainPlan::REFUSED) return fail(I2LQR_ERR_UNSUPPORTED, "%s", plan.why);
     IterArgs<T> a = iter_args<T>(io);
     a.chain_len = k;
+    a.chains = h->col.opt_group_chains != 0;
     if (plan.kind == ChainPlan::WAVE) {
       if (int rc = wave_lds_check(h, true)) return rc;
       HIP_TRY(wave_opt_launch<T>(h->cfg, a, h->model, true, h->fit.lds_wave, s));

@@ -24,6 +24,7 @@ struct ColumnTune {
   int opt_group_ws = -1;  // eight-lane kernel: workspace form (records / gains in HBM)
   int opt_group_overlap = -1;  // sixteen-lane kernel: overlapped schedule (helpers take the records, the terminal block and the gain stores); 0: the one-helper schedule; automatic: on
   int opt_group_fixed = -1;    // sixteen-lane kernel: the fixed-horizon form (k_group_iterate_fixed) where the horizon is one it is built for; 0: the run-time-horizon kernel; automatic: on
+  int opt_group_chains = -1;   // eight- / sixteen-lane kernels: the independent chains of a record side by side, the entry rollout's sin / cos spread over the row, sin / cos of x_0 from the nominal's cache (IterArgs::chains); 0: the serial forms; automatic: on
   int opt_wave_chain = 0;  // i2lqr_solve_chained: 1 = what the speculative chain kernel is not built for runs on the one-problem-per-wavefront kernel's chained form (k_chain_box); 0: refused
 };
 

@@ -57,6 +57,7 @@ template <class T> inline void arg(const IterArgs<T>& a) {
   ptr("IterArgs.cost_it", a.cost_it); ptr("IterArgs.pick_part", a.pick_part);
   ptr("IterArgs.pick_ticket", a.pick_ticket); ptr("IterArgs.best_idx", a.best_idx);
   ptr("IterArgs.best_cost", a.best_cost); val("IterArgs.chain_len", a.chain_len);
+  val("IterArgs.chains", a.chains);
 }
 #ifdef I2LQR_DRY_RUN_LANE  // (translation units that see i2lqr_lane.hpp)
 template <class T> inline void arg(const LaneSet<T>& s) {

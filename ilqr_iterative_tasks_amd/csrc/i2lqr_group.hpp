@@ -345,7 +345,12 @@ template <class T, class Sys, bool WS = false, int G = kGroup, int NH = 0> struc
   }
 
   // -- nominal rollout + cost (control/iterative_ilqr.py:32-48), all lanes of the group redundantly
-  __device__ __forceinline__ T rollout(int XUo, int TRo, const T (&xT)[n]) const {
+  //    chains (IterArgs::chains, wave-uniform): the sixteen-lane form of the plants whose headings do
+  //    not wait for sin / cos takes rollout_row
+  __device__ __forceinline__ T rollout(int XUo, int TRo, const T (&xT)[n], bool chains) const {
+    if constexpr (G == 16 && Sys::kTrigFreeTail) {
+      if (__builtin_expect(chains, 1)) return rollout_row(XUo, TRo, xT);
+    }
     T x[n], u[m], xn[n], tr[NT];
 #pragma unroll
     for (int i = 0; i < n; i++) x[i] = S[XUo + i];
@@ -372,6 +377,88 @@ template <class T, class Sys, bool WS = false, int G = kGroup, int NH = 0> struc
     return cost;
   }
 
+  // -- the same rollout, sixteen lanes per problem, plants with Sys::kTrigFreeTail: rows 2 .. n-1 of
+  //    the step read neither sin / cos nor the position, so with the inputs given every heading of
+  //    the horizon is known after a chain of a few multiply-adds per step, and the N + 1 sin / cos
+  //    evaluations — the long dependent chain of the serial loop's step — are independent: lane g of
+  //    the row takes those of the steps g, g + 16, ...  The positions follow in a second serial pass
+  //    whose step is the two multiply-adds of rows 0 and 1.  Every value is formed by the
+  //    expressions of rollout() (the very Sys::step_tr, Sys::trig, clip): the same bits.
+  //    Main wavefront only, wave_sync() only: no workgroup barrier.
+  __device__ __forceinline__ T rollout_row(int XUo, int TRo, const T (&xT)[n]) const {
+    static_assert(G == 16 && Sys::kTrigFreeTail, "see Sys::kTrigFreeTail");
+    const int N = loop_N();
+    // 1. the clip of the inputs, in LDS: lane g takes the steps g, g + 16, ...
+    for (int t = g; t < N; t += G) {
+      T u[m];
+#pragma unroll
+      for (int a = 0; a < m; a++) u[a] = clip(S[XUo + t * W + n + a], -c.u_max[a], c.u_max[a]);
+#pragma unroll
+      for (int a = 0; a < m; a++) S[XUo + t * W + n + a] = u[a];
+    }
+    wave_sync();
+    T x[n], u[m], xn[n], tr[NT];
+    // 2. rows 2 .. n-1 of every state (all lanes redundantly): step_tr with a zero tr, rows 0 and 1
+    //    of its result dropped
+#pragma unroll
+    for (int i = 0; i < n; i++) x[i] = S[XUo + i];
+#pragma unroll
+    for (int q = 0; q < NT; q++) tr[q] = T(0);
+    for (int t = 0; t < N; t++) {
+#pragma unroll
+      for (int a = 0; a < m; a++) u[a] = S[XUo + t * W + n + a];
+      Sys::step_tr(c, x, u, tr, xn);
+#pragma unroll
+      for (int i = 2; i < n; i++) S[XUo + (t + 1) * W + i] = xn[i];
+#pragma unroll
+      for (int i = 2; i < n; i++) x[i] = xn[i];
+    }
+    // 3. sin / cos of the states g, g + 16, ... <= N (a lane past the end takes state N again and
+    //    stores the same values: no divergent control flow around the wave-uniform branch of
+    //    t_sincos)
+    const int rounds = (N + G) / G;  // ceil((N + 1) / G)
+    for (int r = 0; r < rounds; r++) {
+      const int t0 = g + r * G;
+      const int t = t0 < N ? t0 : N;
+      T xe[n];
+      xe[0] = T(0); xe[1] = T(0);  // (not read by trig: kTrigFreeTail)
+#pragma unroll
+      for (int i = 2; i < n; i++) xe[i] = S[XUo + t * W + i];
+      Sys::trig(xe, tr);
+#pragma unroll
+      for (int q = 0; q < NT; q++) S[TRo + t * NT + q] = tr[q];
+    }
+    wave_sync();
+    // 4. the positions: steps 0 .. N-1 with the cached sin / cos, inputs and sin / cos read one step
+    //    ahead (the look-ahead of the last step reads record N: its input slot is unused, its
+    //    sin / cos that of x_N)
+    T un[m], trn[NT];
+#pragma unroll
+    for (int i = 0; i < n; i++) x[i] = S[XUo + i];
+#pragma unroll
+    for (int a = 0; a < m; a++) u[a] = S[XUo + n + a];
+#pragma unroll
+    for (int q = 0; q < NT; q++) tr[q] = S[TRo + q];
+    for (int t = 0; t < N; t++) {
+#pragma unroll
+      for (int a = 0; a < m; a++) un[a] = S[XUo + (t + 1) * W + n + a];
+#pragma unroll
+      for (int q = 0; q < NT; q++) trn[q] = S[TRo + (t + 1) * NT + q];
+      Sys::step_tr(c, x, u, tr, xn);
+#pragma unroll
+      for (int i = 0; i < n; i++) S[XUo + (t + 1) * W + i] = xn[i];
+#pragma unroll
+      for (int i = 0; i < n; i++) x[i] = xn[i];
+#pragma unroll
+      for (int a = 0; a < m; a++) u[a] = un[a];
+#pragma unroll
+      for (int q = 0; q < NT; q++) tr[q] = trn[q];
+    }
+    const T cost = terminal_cost(x, xT);
+    wave_sync();
+    return cost;
+  }
+
   // -- per-step records, lanes of the group take the horizon steps in turn --------------------
   // pa, pb = 1 / width^2, 1 / height^2 of the obstacle: the same for every step, computed once by
   // the kernel.  The sin / cos of x_{t+1} come from the trajectory's cache (TRo).  Input barrier:
@@ -386,8 +473,123 @@ template <class T, class Sys, bool WS = false, int G = kGroup, int NH = 0> struc
   // stores zeros.
   // first / stride: which records this lane takes (g, 8 in the plain kernel; the speculative
   // kernel spreads them over the lanes of all its wavefronts)
+  // chains (IterArgs::chains, wave-uniform): the record as prep_chains forms it — the same values
   __device__ __forceinline__ void prep(int XUo, int TRo, const T (&ob)[6], T pa, T pb, int first,
-                                       int stride) const {
+                                       int stride, bool chains) const {
+    if (__builtin_expect(chains, 1)) {
+      // the form of the input barrier is decided here, once per call: a record is one basic block
+      if (sizeof(T) == 8 && __builtin_expect(c.fast_barrier, 1))
+        prep_chains<true>(XUo, TRo, ob, pa, pb, first, stride);
+      else
+        prep_chains<false>(XUo, TRo, ob, pa, pb, first, stride);
+    } else {
+      prep_serial(XUo, TRo, ob, pa, pb, first, stride);
+    }
+    wave_sync();
+    ws_publish();
+  }
+
+  // The record with its independent chains side by side.  A record holds three exponentials (the
+  // obstacle's and one per input; five where the input barrier takes its general form) and, in the
+  // short form, two reciprocals: dependent chains of 13 multiply-adds each that prep_serial
+  // evaluates one after the other — a wavefront alone on its SIMD then waits out every
+  // multiply-add's latency.  Here the arguments are formed first and the chains advance together,
+  // one Horner step of all of them at a time (t_exp_d, t_rcp2).  Every value by the operations of
+  // prep_serial in their order: the same bits.
+  // FASTB: fp64 with c.fast_barrier (the short form of the input barrier, see above).
+  template <bool FASTB>
+  __device__ __forceinline__ void prep_chains(int XUo, int TRo, const T (&ob)[6], T pa, T pb,
+                                              int first, int stride) const {
+    static_assert(m == 2, "two inputs");
+    const bool has_ob = ob[5] >= T(0);
+    const int opt = has_ob ? (int)ob[5] : 0;
+    const T spd_y = opt == 1 ? ob[4] : T(0), spd_x = opt == 2 ? ob[4] : T(0);
+    const int rounds = (N + stride) / stride;  // ceil((N + 1) / stride)
+    for (int r = 0; r < rounds; r++) {
+      const int t0 = first + r * stride;
+      const int t = t0 < N ? t0 : N;          // record index (obstacle term of x_t)
+      const int ts = t0 < N ? t0 : N - 1;     // step index (Jacobian entries, input barrier)
+      T* Rs = rec(ts);
+      T* R = rec(t);
+      // (a marker in the listing; the two forms' different texts also keep the compiler from
+      // merging the heads of the two loop bodies in front of the branch that chooses between them)
+      if constexpr (FASTB) asm volatile("; record, short input barrier" ::: "memory");
+      else asm volatile("; record, general input barrier" ::: "memory");
+      T xe[n], tr[NT], u[m], jv[NV];
+#pragma unroll
+      for (int i = 0; i < n; i++) xe[i] = S[XUo + (ts + 1) * W + i];
+#pragma unroll
+      for (int a = 0; a < m; a++) u[a] = S[XUo + ts * W + n + a];
+#pragma unroll
+      for (int q = 0; q < NT; q++) tr[q] = S[TRo + (ts + 1) * NT + q];
+      const T px = S[XUo + t * W + 0], py = S[XUo + t * W + 1];
+      // the arguments of the exponentials
+      const T dz = opt == 2 ? px - (ob[0] - T(t) * spd_x) : px - ob[0];
+      const T dy = opt == 1 ? py - (ob[1] + T(t) * spd_y) : py - ob[1];
+      const T h = T(1) + c.safety_margin - (dz * pa * dz + dy * pb * dy);
+      const T hd0 = T(-2) * pa * dz, hd1 = T(-2) * pb * dy;
+      T e, e_hi[m], e_lo[m];
+      if constexpr (FASTB) {
+        // (FASTB only with T = double; the casts keep the fp32 instantiation well-formed)
+        const double xa[3] = {(double)(c.obs_q2 * h), (double)(c.ctrl_q2 * (u[0] - c.u_max[0])),
+                              (double)(c.ctrl_q2 * (u[1] - c.u_max[1]))};
+        double ea[3], rc[2];
+        t_exp_d<false, 3, 2, true>(xa, ea);
+        t_rcp2(ea[1], ea[2], &rc[0], &rc[1]);
+        e = (T)ea[0];
+#pragma unroll
+        for (int a = 0; a < m; a++) {
+          e_hi[a] = (T)ea[1 + a];
+          e_lo[a] = c.ctrl_c[a] * (T)rc[a];
+        }
+      } else if constexpr (sizeof(T) == 8) {
+        const double xa[5] = {(double)(c.obs_q2 * h), (double)(c.ctrl_q2 * (u[0] - c.u_max[0])),
+                              (double)(c.ctrl_q2 * (-c.u_max[0] - u[0])),
+                              (double)(c.ctrl_q2 * (u[1] - c.u_max[1])),
+                              (double)(c.ctrl_q2 * (-c.u_max[1] - u[1]))};
+        double ea[5];
+        t_exp_d<false, 5, 0, true>(xa, ea);
+        e = (T)ea[0];
+#pragma unroll
+        for (int a = 0; a < m; a++) {
+          e_hi[a] = (T)ea[1 + 2 * a];
+          e_lo[a] = (T)ea[2 + 2 * a];
+        }
+      } else {  // fp32: the hardware exponential, no chain to interleave
+        e = t_exp(c.obs_q2 * h);
+#pragma unroll
+        for (int a = 0; a < m; a++) {
+          e_hi[a] = t_exp(c.ctrl_q2 * (u[a] - c.u_max[a]));
+          e_lo[a] = t_exp(c.ctrl_q2 * (-c.u_max[a] - u[a]));
+        }
+      }
+      Sys::jac_var(c, xe, u, tr, jv);  // at (x_{t+1}, u_t): control/iterative_ilqr.py:92-99
+#pragma unroll
+      for (int q = 0; q < NV; q++) Rs[GL::R_JV + q] = jv[q];
+#pragma unroll
+      for (int a = 0; a < m; a++) {  // add_control_constraint(): control/ilqr_helper.py:83-103
+        Rs[GL::R_LU + a] = c.ctrl_q12 * e_hi[a] - c.ctrl_q12 * e_lo[a];
+        Rs[GL::R_LUU + a] = c.ctrl_q122 * e_hi[a] +
+                            c.ctrl_q122 * e_lo[a];
+      }
+      R[GL::R_ZERO] = T(0);
+      R[GL::R_ONE] = T(1);
+      // obstacle barrier: control/ilqr_helper.py:32-51 (stage) / :121-147 (terminal, index N)
+      const T c1 = c.obs_q12 * e, c2 = c.obs_q122 * e;
+      R[GL::R_OB + 0] = has_ob ? c1 * hd0 : T(0);
+      R[GL::R_OB + 1] = has_ob ? c1 * hd1 : T(0);
+      R[GL::R_OB + 2] = has_ob ? c2 * (hd0 * hd0) : T(0);
+      R[GL::R_OB + 3] = has_ob ? c2 * (hd0 * hd1) : T(0);
+      R[GL::R_OB + 4] = has_ob ? c2 * (hd1 * hd1) : T(0);
+      // (and the tails: the last store of a record stays in the record's block)
+      if constexpr (FASTB) asm volatile("; record end, short input barrier" ::: "memory");
+      else asm volatile("; record end, general input barrier" ::: "memory");
+    }
+  }
+
+  // the record with its chains one after the other ("group_chains" 0)
+  __device__ __forceinline__ void prep_serial(int XUo, int TRo, const T (&ob)[6], T pa, T pb,
+                                              int first, int stride) const {
     const bool has_ob = ob[5] >= T(0);
     const int opt = has_ob ? (int)ob[5] : 0;
     const T spd_y = opt == 1 ? ob[4] : T(0), spd_x = opt == 2 ? ob[4] : T(0);
@@ -441,8 +643,6 @@ template <class T, class Sys, bool WS = false, int G = kGroup, int NH = 0> struc
       R[GL::R_OB + 3] = has_ob ? c2 * (hd0 * hd1) : T(0);
       R[GL::R_OB + 4] = has_ob ? c2 * (hd1 * hd1) : T(0);
     }
-    wave_sync();
-    ws_publish();
   }
 
   // regularised inverse of Q_uu, m == 2 (control/iterative_ilqr.py:118-123)
@@ -898,8 +1098,13 @@ template <class T, class Sys, bool WS = false, int G = kGroup, int NH = 0> struc
   //        sin / cos cache itself.
   //    Same operations on the same operands as forward<false>: bit-identical states and inputs
   //    (~75 instructions per step against 117).
+  //    chains (IterArgs::chains, wave-uniform): sin / cos of x_0 — the same x_0 in every pass — are
+  //    read from slot 0 of the nominal's cache TRo (written by the entry rollout or by the pass that
+  //    produced the nominal) instead of evaluated again.  The cache holds the short kernel's value
+  //    wherever that is valid and the general one elsewhere: what the pass, or its general repeat,
+  //    would compute.
   __device__ __forceinline__ T forward_row(int XUo, int XUn, int TRn, const T (&xT)[n],
-                                           bool* bad) const {
+                                           bool* bad, bool chains, int TRo) const {
     static_assert(G == 16 && m == 2, "two inputs on the two halves of a 16-lane row");
     const int half = g >> 3;
     const T umax = half ? c.u_max[1] : c.u_max[0];
@@ -908,7 +1113,17 @@ template <class T, class Sys, bool WS = false, int G = kGroup, int NH = 0> struc
     for (int i = 0; i < n; i++) x[i] = S[XUo + i];
 #pragma unroll
     for (int i = 0; i < n; i++) S[XUn + i] = x[i];
-    Sys::template trig_g<false>(x, tr, bad);
+    // (I2LQR_FORWARD_X0_TRIG: an A/B build, `make variant`, that keeps the evaluation with the
+    // other two parts of "group_chains" on — the measurement of this part on its own)
+#ifdef I2LQR_FORWARD_X0_TRIG
+    chains = false;
+#endif
+    if (__builtin_expect(chains, 1)) {
+#pragma unroll
+      for (int q = 0; q < NT; q++) tr[q] = S[TRo + q];
+    } else {
+      Sys::template trig_g<false>(x, tr, bad);
+    }
 #pragma unroll
     for (int q = 0; q < NT; q++) S[TRn + q] = tr[q];
     // Running bases, bumped once per pair of steps; every access of a step is a base plus a
@@ -990,11 +1205,12 @@ template <class T, class Sys, bool WS = false, int G = kGroup, int NH = 0> struc
   // -- forward pass: control/iterative_ilqr.py:133-160; all lanes of the group redundantly ------
   //    GENERAL = false: short sincos kernel only, *bad set if an angle left its range (the caller
   //    repeats the pass with GENERAL = true); see t_sincos_fast.
+  //    chains, TRo: forward_row only (the nominal's sin / cos cache)
   template <bool GENERAL>
   __device__ __forceinline__ T forward(int XUo, int XUn, int TRn, const T (&xT)[n],
-                                       bool* bad) const {
+                                       bool* bad, bool chains = false, int TRo = 0) const {
     if constexpr (G == 16 && !GENERAL && Sys::kHeadingAhead && m == 2)
-      return forward_row(XUo, XUn, TRn, xT, bad);
+      return forward_row(XUo, XUn, TRn, xT, bad, chains, TRo);
     const int N = loop_N();
     T x[n], u[m], xn[n], tr[NT];
 #pragma unroll
@@ -1169,7 +1385,8 @@ __device__ __forceinline__ void group_iterate_body(const DevCfg<T, Sys::n, Sys::
         if (!(flags & 1)) break;
         if (flags & 2) {
           const int pc = ctl[lane / G];
-          w.prep(pc ? L.XU1 : L.XU0, pc ? L.TR1 : L.TR0, ob, ob_pa, ob_pb, h0 * G + g, hs * G);
+          w.prep(pc ? L.XU1 : L.XU0, pc ? L.TR1 : L.TR0, ob, ob_pa, ob_pb, h0 * G + g, hs * G,
+                 a.chains != 0);
         }
         __syncthreads();  // B2: the records are complete
       }
@@ -1205,7 +1422,8 @@ __device__ __forceinline__ void group_iterate_body(const DevCfg<T, Sys::n, Sys::
   T vb[n];
 #pragma unroll
   for (int i = 0; i < n; i++) vb[i] = T(0);
-  T cost = w.rollout(L.XU0, L.TR0, xT);
+  const bool chains = a.chains != 0;
+  T cost = w.rollout(L.XU0, L.TR0, xT, chains);
   int it = 0, status = a.early_exit ? 2 /*MAX_ITER*/ : 0 /*RUNNING*/;
   T cost_ret = cost;
   bool fresh = true, active = a.n_iters > 0;
@@ -1222,7 +1440,7 @@ __device__ __forceinline__ void group_iterate_body(const DevCfg<T, Sys::n, Sys::
     {
       auto& st_t0 = w.st_t0; auto& st_t1 = w.st_t1; auto& st_acc = w.st_acc;
       STAMP_BEGIN();
-      if (__any(fresh)) w.prep(XUo, TRo, ob, ob_pa, ob_pb, g, G);
+      if (__any(fresh)) w.prep(XUo, TRo, ob, ob_pa, ob_pb, g, G, chains);
       STAMP_END(0);
     }
 #else
@@ -1234,11 +1452,11 @@ __device__ __forceinline__ void group_iterate_body(const DevCfg<T, Sys::n, Sys::
       if constexpr (OVL) {
         if (do_prep) w.terminal_base(XUo, xT, vb);
       } else {
-        if (do_prep) w.prep(XUo, TRo, ob, ob_pa, ob_pb, g, H * G);
+        if (do_prep) w.prep(XUo, TRo, ob, ob_pa, ob_pb, g, H * G, chains);
       }
       __syncthreads();  // B2
     } else {
-      if (__any(fresh)) w.prep(XUo, TRo, ob, ob_pa, ob_pb, g, G);
+      if (__any(fresh)) w.prep(XUo, TRo, ob, ob_pa, ob_pb, g, G, chains);
     }
 #endif
     // optimistic, branch-free passes first; the general forms only if a lane asked for them
@@ -1256,7 +1474,7 @@ __device__ __forceinline__ void group_iterate_body(const DevCfg<T, Sys::n, Sys::
       STAMP_BEGIN();
 #endif
       bool big = false;
-      cost_new = w.template forward<false>(XUo, XUn, TRn, xT, &big);
+      cost_new = w.template forward<false>(XUo, XUn, TRn, xT, &big, chains, TRo);
       if (__builtin_expect(__any(big), 0)) cost_new = w.template forward<true>(XUo, XUn, TRn, xT, &big);
 #ifdef I2LQR_STAMPS
       STAMP_END(6);
@@ -1533,7 +1751,7 @@ __global__ __launch_bounds__(64 * V) void k_group_spec(const DevCfg<T, Sys::n, S
   const T ob_pa = T(1) / (ob[2] * ob[2]), ob_pb = T(1) / (ob[3] * ob[3]);
   __syncthreads();
   if (v == 0) {
-    const T c0 = w.rollout(SLay.xu_off(0), SLay.tr_off(0), xT);
+    const T c0 = w.rollout(SLay.xu_off(0), SLay.tr_off(0), xT, a.chains != 0);
     if (g == 0) CN[V * PW + p] = c0;
   }
   __syncthreads();
@@ -1548,7 +1766,7 @@ __global__ __launch_bounds__(64 * V) void k_group_spec(const DevCfg<T, Sys::n, S
   bool fresh = true, active = it_cap > 0;
   while (__any(active)) {
     if (__any(fresh)) {
-      w.prep(SLay.xu_off(nb), SLay.tr_off(nb), ob, ob_pa, ob_pb, v * G + g, V * G);
+      w.prep(SLay.xu_off(nb), SLay.tr_off(nb), ob, ob_pa, ob_pb, v * G + g, V * G, a.chains != 0);
       __syncthreads();
     }
     // this wavefront's iteration: the one that follows v rejects
@@ -1561,7 +1779,7 @@ __global__ __launch_bounds__(64 * V) void k_group_spec(const DevCfg<T, Sys::n, S
     if (__builtin_expect(__any(w.template backward<false>(XUo, xT, lamb_v, active)), 0))
       w.template backward<true>(XUo, xT, lamb_v, active);
     bool big = false;
-    T cost_new = w.template forward<false>(XUo, XUn, TRn, xT, &big);
+    T cost_new = w.template forward<false>(XUo, XUn, TRn, xT, &big, a.chains != 0, SLay.tr_off(nb));
     if (__builtin_expect(__any(big), 0)) cost_new = w.template forward<true>(XUo, XUn, TRn, xT, &big);
     if (g == 0) CN[v * PW + p] = cost_new;
     __syncthreads();

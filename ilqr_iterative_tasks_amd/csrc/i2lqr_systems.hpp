@@ -139,6 +139,13 @@ __device__ __forceinline__ double t_fma3(double a, double b, double c) {
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
   return d;
 }
+// ... with the coefficient in a SCALAR register pair, where the compiler keeps the literals of a
+// kernel that has the scalar registers for them: no copy at all
+__device__ __forceinline__ double t_fma3s(double a, double b, double c) {
+  double d;
+  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(c));
+  return d;
+}
 __device__ __forceinline__ void t_sincos_fast_h3(double x, double* s, double* c, bool* big_out) {
   const bool big = !(__builtin_fabs(x) < 1.0e5);
   *big_out = *big_out || big;
@@ -227,11 +234,20 @@ template <class T> __device__ __forceinline__ T t_exp(T x);
 // overflow / underflow / NaN through ldexp and the clamped exponent).
 // exp of NE arguments at once with the SLIT literals shared: e[q] = t_exp(x[q]) for q < NE - NB,
 // t_exp_bounded(x[q]) for the last NB (bit for bit the single-argument functions below)
-template <bool SLIT, int NE, int NB>
+// H3 (without SLIT): the Horner steps as three-address multiply-adds (t_fma3s, above) — the NE chains
+// of a step side by side with no coefficient copy between them — and the clamp of the argument as
+// two selects, which the compiler does not turn into branches (the records of the eight- /
+// sixteen-lane kernels, GroupWorker::prep_chains: one basic block).  Same operations, bit for bit.
+template <bool SLIT, int NE, int NB, bool H3 = false>
 __device__ __forceinline__ void t_exp_d(const double (&x0)[NE], double (&e)[NE]) {
+  static_assert(!(SLIT && H3), "the three-address form takes its coefficients from vector registers");
   double x[NE], kf[NE], r[NE], p[NE];
 #pragma unroll
   for (int q = 0; q < NE; q++)
+    if constexpr (H3) {
+      const double lo = x0[q] < -746.0 ? -746.0 : x0[q];  // NaN passes through both selects
+      x[q] = q < NE - NB ? (lo > 710.0 ? 710.0 : lo) : x0[q];
+    } else
     x[q] = q < NE - NB ? (x0[q] < I2LQR_LIT(SLIT, -746.0, x0[q]) ? -746.0
                           : (x0[q] > I2LQR_LIT(SLIT, 710.0, x0[q]) ? 710.0 : x0[q]))
                        : x0[q];  // NaN passes through
@@ -250,7 +266,8 @@ __device__ __forceinline__ void t_exp_d(const double (&x0)[NE], double (&e)[NE])
 #define I2LQR_EXP_STEP(lit)                                          \
   {                                                                  \
     const double ck = I2LQR_LIT(SLIT, lit, p[0]);                    \
-    _Pragma("unroll") for (int q = 0; q < NE; q++) p[q] = __builtin_fma(p[q], r[q], ck); \
+    _Pragma("unroll") for (int q = 0; q < NE; q++)                   \
+      p[q] = H3 ? t_fma3s(p[q], r[q], ck) : __builtin_fma(p[q], r[q], ck); \
   }
   I2LQR_EXP_STEP(2.0876756987868098979e-09)
   I2LQR_EXP_STEP(2.5052108385441718775e-08)
@@ -317,6 +334,21 @@ template <> __device__ __forceinline__ double t_rcp<double>(double x) {
   e = __builtin_fma(-x, r, 1.0);
   const double r2 = __builtin_fma(r, e, r);
   return (r2 == r2) ? r2 : r;  // x = 0 / inf: keep the seed's inf / 0 instead of the NaN of 0 * inf
+}
+// t_rcp of two operands, the two refinements statement by statement (bit for bit t_rcp each)
+__device__ __forceinline__ void t_rcp2(double x0, double x1, double* o0, double* o1) {
+  double r0 = __builtin_amdgcn_rcp(x0);
+  double r1 = __builtin_amdgcn_rcp(x1);
+  double e0 = __builtin_fma(-x0, r0, 1.0);
+  double e1 = __builtin_fma(-x1, r1, 1.0);
+  r0 = __builtin_fma(r0, e0, r0);
+  r1 = __builtin_fma(r1, e1, r1);
+  e0 = __builtin_fma(-x0, r0, 1.0);
+  e1 = __builtin_fma(-x1, r1, 1.0);
+  const double q0 = __builtin_fma(r0, e0, r0);
+  const double q1 = __builtin_fma(r1, e1, r1);
+  *o0 = (q0 == q0) ? q0 : r0;
+  *o1 = (q1 == q1) ? q1 : r1;
 }
 template <> __device__ __forceinline__ float t_rcp<float>(float x) {
   const float r = __builtin_amdgcn_rcpf(x);  // 1 ulp seed, one Newton step
@@ -630,6 +662,9 @@ template <class T> struct Bicycle4 {
   // theta' = theta + delta dt with delta an INPUT: the heading two steps ahead is not known before
   // the next step's feedback law has run
   static constexpr bool kHeadingAhead = false;
+  // rows 2 .. n-1 of step_tr read neither tr nor x[0], x[1]: every heading of a rollout with given
+  // inputs is known before any sin / cos is (GroupWorker::rollout_row)
+  static constexpr bool kTrigFreeTail = true;
 
   // {cos(theta), sin(theta)}
   static __device__ __forceinline__ void trig(const T (&xe)[n], T (&tr)[NTRIG]) {
@@ -712,6 +747,7 @@ template <class T> struct Bicycle6 {
   // so a rollout can evaluate the sin / cos of two consecutive steps side by side (the sixteen-lane
   // forward pass does, on the two halves of a problem's DPP row: GroupWorker::forward_row)
   static constexpr bool kHeadingAhead = true;
+  static constexpr bool kTrigFreeTail = true;  // (as Bicycle4: rows 2 .. n-1 are linear in the inputs)
   static __device__ __forceinline__ T heading(const T (&xe)[n]) { return xe[3]; }
   // heading of the successor state: the very expression step_tr evaluates for xn[3]
   template <class Cfg>
@@ -799,6 +835,7 @@ template <class T> struct Quad12 {
   static constexpr int NVAR = 37;
   static constexpr int system_id = 2;
   static constexpr bool kHeadingAhead = false;
+  static constexpr bool kTrigFreeTail = false;  // the angle rates go through sin / cos of the angles
 
   // {sin phi, cos phi, sin theta, cos theta, sin psi, cos psi}
   static __device__ __forceinline__ void trig(const T (&xe)[n], T (&tr)[NTRIG]) {

@@ -114,6 +114,11 @@ template <class T> struct IterArgs {
   T* best_cost = nullptr;              // [1] out
   // k_group_spec<.., CHAIN>: B chains of chain_len problems each, stored chain after chain
   int chain_len = 1;
+  // eight- / sixteen-lane kernels ("group_chains"): 1 = the independent chains of a record side by
+  // side, the entry rollout with its sin / cos spread over the row, sin / cos of x_0 from the
+  // nominal's cache (GroupWorker::prep_chains / rollout_row / forward_row); 0 = the serial forms.
+  // Wave-uniform; the same values either way.
+  int chains = 1;
 };
 
 // relaxed terminal cost of one candidate, utils/base.py:427-437: ss = ||x_N - x_term||_2^2 summed in

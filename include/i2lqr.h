@@ -315,7 +315,14 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     0 forces k_group_iterate.  Same operations in the same order, bit-identical;
  *                     same batch thresholds and helper wavefronts.  For any other horizon the
  *                     option has no effect (and is no error).
- *   "speculate"       ("group_lanes" 8 / automatic) 1: the speculative form of the eight-lane
+ *   "group_chains"    eight- / sixteen-lane kernels (plain and speculative): 1 / automatic: the
+ *                     three exponentials and two reciprocals of a per-step record advance side by
+ *                     side instead of one after the other; sixteen lanes: the entry rollout
+ *                     computes every heading first and spreads the sin / cos evaluations over the
+ *                     lanes of a problem, and the forward pass reads sin / cos of x_0 from the
+ *                     nominal's cache.  0 forces the serial forms.  Same operations on every value,
+ *                     bit-identical.
+ *   "speculate"      ("group_lanes" 8 / automatic) 1: the speculative form of the eight-lane
  *                     kernel — V wavefronts per eight problems (three up to 512 problems, two
  *                     above and in the tail of the chunked solves), wavefront v runs the iteration
  *                     that follows v rejects (same nominal trajectory, lamb * 10^v:

@@ -49,7 +49,7 @@ OPTIONS = {"defer_states": (0, 1), "reroll_nominal": (0, 1), "lds_gain_steps": (
            "chunk_step": (1, 2, 4, 9), "speculate": (0, 1), "group_workspace": (0, 1),
            "group_lanes": (8, 16, 64), "fused_compaction": (0, 1), "final_round": (0, 1, 2, 3, 5),
            "line_search": (0, 2, 4, 8), "obstacles": (0, 2, 3, 8), "group_overlap": (0, 1),
-           "group_fixed_horizon": (0, 1), "wave_chain": (0, 1)}
+           "group_fixed_horizon": (0, 1), "wave_chain": (0, 1), "group_chains": (0, 1)}
 
 
 class Arena:
@@ -255,7 +255,7 @@ def column_case(system, options, B, entry, workspace=True, chain_len=1, N=20, dt
 
 # Every kernel, wavefront count and form the problem-major launcher chooses between, once each (the
 # random configurations below reach most of them, not reliably all)
-for opts in ({}, {"group_fixed_horizon": 0}, {"group_overlap": 0}):
+for opts in ({}, {"group_fixed_horizon": 0}, {"group_overlap": 0}, {"group_chains": 0}):
     for B0 in (1024, 1025, 2048, 2049):  # sixteen-lane kernel: 3 / 2 / 1 wavefronts, both forms
         assert column_case("bicycle6", opts, B0, "iterate")[0] == 0
 for B0, ws in ((2048, True), (2049, True), (4161, True), (4161, False)):  # eight-lane: 3 / 1, workspace form
