@@ -37,17 +37,29 @@ class HipCandidateSolver:
     wave_chain = True: every problem-major handle gets the "wave_chain" option, so solve_chained
     runs laps of equal length in ONE launch (k_chain_box, one wavefront per lap) with line_search,
     several obstacles, a state box, stage weights or quad12 as well; ragged laps keep the launch
-    per chain step."""
+    per chain step.
+
+    barrier_cost = True (not the reference's model either): every handle is created problem-major
+    with the "barrier_cost" option set (include/i2lqr.h: the line search, the accept / reject step
+    and the convergence test see the barriers, k_iterate_merit; `cost` is the merit J).  solve()
+    works, solve_chained() runs a launch per chain step (the chain kernels have no barrier cost:
+    not together with wave_chain), candidate_round / sharded_round run on the handle as they do
+    with line_search."""
 
     def __init__(self, device="cuda:0", dtype="f64", line_search=1, state_box=None,
-                 wave_chain=False):
+                 wave_chain=False, barrier_cost=False):
         if int(line_search) not in (-1, 0, 1, 2, 4, 8):
             raise ValueError(f"line_search is 2, 4 or 8 step sizes, or -1 / 0 / 1 (off): got {line_search}")
+        if barrier_cost and wave_chain:
+            raise ValueError("barrier_cost and wave_chain do not go together: the chain kernel "
+                             "(k_chain_box) has no barrier cost; without wave_chain solve_chained "
+                             "runs a launch per chain step")
         self.device = device
         self.dtype = dtype
         self.line_search = int(line_search) if int(line_search) > 1 else 1
         self.state_box = state_box if state_box is not None and state_box.active else None
         self.wave_chain = bool(wave_chain)
+        self.barrier_cost = bool(barrier_cost)
         self._solvers = {}
 
     @staticmethod
@@ -78,8 +90,8 @@ class HipCandidateSolver:
         for batches of that size (i2lqr_recommended_layout): a caller who hands 65536 candidates
         to solve() gets the one-problem-per-lane kernels without knowing that they exist."""
         from ..solver import BatchedILQR
-        # k_iterate_ls / k_iterate_obs / k_iterate_box are problem-major kernels
-        if self.line_search > 1 or n_obs > 1 or self.state_box is not None:
+        # k_iterate_ls / k_iterate_obs / k_iterate_box / k_iterate_merit are problem-major kernels
+        if self.line_search > 1 or n_obs > 1 or self.state_box is not None or self.barrier_cost:
             if cfg.layout != 0:
                 cfg = cfg.copy()
                 cfg.layout = 0
@@ -91,6 +103,7 @@ class HipCandidateSolver:
         key = bytes(C.string_at(C.byref(cfg), C.sizeof(cfg))) + bytes([n_obs if n_obs > 1 else 0])
         if self.state_box is not None:
             key += self.state_box.key()
+        key += bytes([1 if self.barrier_cost else 0])
         if key not in self._solvers:
             self._solvers[key] = BatchedILQR(cfg, self.device)
             if self.wave_chain and cfg.layout == 0:
@@ -104,6 +117,8 @@ class HipCandidateSolver:
                 if b.lo.size != cfg.n:
                     raise ValueError(f"the state box has {b.lo.size} components, the plant {cfg.n}")
                 self._solvers[key].set_state_box(b.lo, b.hi, b.q1, b.q2)
+            if self.barrier_cost:
+                self._solvers[key].set_option("barrier_cost", 1)
         return self._solvers[key]
 
     def _round_buffers(self, cfg, x0, x_terms, qfun, lamb0, obs_rec, early_exit):
@@ -483,7 +498,9 @@ class HipCandidateSolver:
             h["obs"].reshape(osh)[:] = np.asarray(obs_rec, float)
         nb = pk["in_bytes"]
         if pk.get("one_launch") is None:
-            pk["one_launch"] = len(set(widths)) == 1 and getattr(self, "use_chain_kernel", True)
+            # (the chain kernels have no barrier cost: a launch per chain step)
+            pk["one_launch"] = (len(set(widths)) == 1 and getattr(self, "use_chain_kernel", True)
+                                and not self.barrier_cost)
             if pk["one_launch"]:  # the steps' views are consecutive slices of ONE block: the whole of it
                 first = pk["steps"][0]
                 whole = {name: torch.as_strided(first[name], (B,) + tuple(first[name].shape[1:]),

@@ -600,6 +600,12 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
     if (v > 1 && !problem_major(h)) return refuse_layout(wave_phrase(WAVE_OBS));
     h->model.obs = v > 1 ? v : 0;
   }
+  else if (!strcmp(name, "barrier_cost")) {
+    if (v != -1 && v != 0 && v != 1)
+      return fail(I2LQR_ERR_INVALID, "\"barrier_cost\" is 1 (on), or -1 / 0 (off)");
+    if (v == 1 && !problem_major(h)) return refuse_layout(wave_phrase(WAVE_MERIT));
+    h->model.barrier_cost = v == 1;
+  }
   else if (!strcmp(name, "wave_chain")) {
     if (v != -1 && v != 0 && v != 1)
       return fail(I2LQR_ERR_INVALID, "\"wave_chain\" is 1 (on), or -1 / 0 (off)");
@@ -739,7 +745,8 @@ int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void
   if (chains == 0) return I2LQR_OK;
   const SolveIO io{chains, h->cfg.max_iter, 1, X, U, x_term, lamb, obs, cost, K, k, iters, status};
   if (int rc = check_io(io)) return rc;
-  // (k_chain_box carries the models: nothing to refuse with "wave_chain" 1)
+  // (k_chain_box carries the models but the barrier cost: nothing else to refuse with "wave_chain" 1)
+  if (h->model.barrier_cost) return fail(I2LQR_ERR_UNSUPPORTED, "%s", kChainNoBarrierCost);
   if (const WaveForm f = h->model.form(); f != WAVE_PLAIN && h->col.opt_wave_chain != 1)
     return fail(I2LQR_ERR_UNSUPPORTED, "chains run on the sixteen-lane speculative kernel, which %s, "
                 "or solve the chain steps one after the other", wave_lack_phrase(f));

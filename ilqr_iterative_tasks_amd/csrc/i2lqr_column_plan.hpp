@@ -138,7 +138,7 @@ struct ColumnChoice {
 // ws_bytes: of the registered workspace, -1 without one
 inline ColumnChoice column_kernel(const DeviceGeometry& g, const ColumnFit& fit, const ColumnTune& t,
                                   WaveForm f, int64_t ws_bytes, int64_t B, bool early_exit) {
-  // a model is on ("line_search", "obstacles", a state box): every call runs on that form of the
+  // a model is on ("line_search", "obstacles", a state box, "barrier_cost"): every call runs on that form of the
   // one-problem-per-wavefront kernel (i2lqr_wave_opt.h), whatever the batch size
   if (f != WAVE_PLAIN) {
     if (t.opt_group == 8 || t.opt_group == 16) {
@@ -300,12 +300,18 @@ inline size_t wave_lds_need(const ColumnFit& f, const WaveModel& model, bool cha
 // i2lqr_solve_chained, `chains` chains in ONE launch: k_group_spec<.., CHAIN> where it is built for
 // the handle; otherwise, and with a model on, "wave_chain" 1 runs k_chain_box (i2lqr_wave_chain.hip)
 // with the handle's state box, "obstacles" and "line_search"
+// Neither chain kernel has the barrier cost (k_chain_box's accept / reject step is k_iterate_box's).
 struct ChainPlan {
   enum Kind { SPEC, WAVE, REFUSED } kind;
   const char* why;  // REFUSED: the message
 };
+constexpr const char* kChainNoBarrierCost =
+    "chains have no barrier cost: neither the speculative chain kernel nor \"wave_chain\" "
+    "(k_chain_box) carries \"barrier_cost\"; solve the chain steps one after the other instead "
+    "(a launch per chain step, lamb carried over)";
 inline ChainPlan chain_plan(const DeviceGeometry& g, const ColumnFit& fit, const ColumnTune& t,
                             WaveForm f, int64_t ws_bytes, int64_t chains) {
+  if (f == WAVE_MERIT) return {ChainPlan::REFUSED, kChainNoBarrierCost};  // with or without "wave_chain"
   const bool bicycle = fit.plant == ColumnFit::BICYCLE;
   const bool wc = t.opt_wave_chain == 1, model = f != WAVE_PLAIN;
   // (not asked about where "wave_chain" takes the model anyway)

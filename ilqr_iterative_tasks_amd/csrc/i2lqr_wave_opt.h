@@ -1,6 +1,7 @@
 // The opt-in forms of the one-problem-per-wavefront kernel - k_iterate_ls, k_iterate_obs,
-// k_iterate_box and the chained k_chain_box, each compiled in a translation unit of its own
-// (i2lqr_wave_ls.hip, i2lqr_wave_obs.hip, i2lqr_wave_box.hip, i2lqr_wave_chain.hip): their
+// k_iterate_box, k_iterate_merit and the chained k_chain_box, each compiled in a translation unit of
+// its own (i2lqr_wave_ls.hip, i2lqr_wave_obs.hip, i2lqr_wave_box.hip, i2lqr_wave_merit.hip,
+// i2lqr_wave_chain.hip): their
 // declarations, the one list of their instantiations and their one launcher (i2lqr_wave_opt.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -56,6 +57,15 @@ __global__ __launch_bounds__(64) void k_iterate_box(const DevCfg<T, Sys::n, Sys:
                                                     const IterArgs<T> a, const int steps,
                                                     const int n_obs, const BoxCfg<T, Sys::n> box);
 
+// k_iterate_box whose line search, accept / reject and convergence test see the merit J = c + P: the
+// barrier-free cost plus the barriers of the inputs, the records and the box ("barrier_cost",
+// include/i2lqr.h); box_q1: the box's q1 (BoxCfg carries its products only).  a.cost returns J.
+template <class T, class Sys, bool HASQR>
+__global__ __launch_bounds__(64) void k_iterate_merit(const DevCfg<T, Sys::n, Sys::m> c,
+                                                      const IterArgs<T> a, const int steps,
+                                                      const int n_obs, const BoxCfg<T, Sys::n> box,
+                                                      const T box_q1);
+
 // a.B chains of a.chain_len problems each, stored chain after chain; one wavefront solves the
 // problems of its chain one after the other as k_iterate_box solves one (to termination:
 // a.early_exit = 1, a.n_iters = max_iter).  lamb is read from a.lamb[] for the first problem of a
@@ -73,6 +83,7 @@ __global__ __launch_bounds__(64) void k_chain_box(const DevCfg<T, Sys::n, Sys::m
 #define I2LQR_WAVE_TAIL_LS(REAL, N_) const int
 #define I2LQR_WAVE_TAIL_OBS(REAL, N_) const int, const int
 #define I2LQR_WAVE_TAIL_BOX(REAL, N_) const int, const int, const BoxCfg<REAL, N_>
+#define I2LQR_WAVE_TAIL_MERIT(REAL, N_) const int, const int, const BoxCfg<REAL, N_>, const REAL
 #define I2LQR_WAVE_OPT_KERNELS_(DECL, KERNEL, TAIL, REAL, SYS, N_, M_)                             \
   DECL void KERNEL<REAL, SYS<REAL>, false>(const DevCfg<REAL, N_, M_>, const IterArgs<REAL>,       \
                                            TAIL(REAL, N_));                                        \
@@ -89,6 +100,7 @@ __global__ __launch_bounds__(64) void k_chain_box(const DevCfg<T, Sys::n, Sys::m
 I2LQR_WAVE_OPT_KERNELS(extern template __global__, k_iterate_ls, I2LQR_WAVE_TAIL_LS)
 I2LQR_WAVE_OPT_KERNELS(extern template __global__, k_iterate_obs, I2LQR_WAVE_TAIL_OBS)
 I2LQR_WAVE_OPT_KERNELS(extern template __global__, k_iterate_box, I2LQR_WAVE_TAIL_BOX)
+I2LQR_WAVE_OPT_KERNELS(extern template __global__, k_iterate_merit, I2LQR_WAVE_TAIL_MERIT)
 I2LQR_WAVE_OPT_KERNELS(extern template __global__, k_chain_box, I2LQR_WAVE_TAIL_BOX)
 
 // Enqueue the form model.form(chained) for a.B problems - chained: a.B chains of a.chain_len

@@ -36,6 +36,10 @@ hipError_t launch_form(const i2lqr_config& cfg, const IterArgs<T>& a, const Wave
       return chained ? launch<k_chain_box<T, Sys, HASQR>>(lds, s, c, a, steps, n_obs, box)
                      : launch<k_iterate_box<T, Sys, HASQR>>(lds, s, c, a, steps, n_obs, box);
     }
+    case WAVE_MERIT: {  // (a chained call never gets here: form(true) is the box form)
+      const auto box = make_box_cfg<T, Sys::n>(model.box);
+      return launch<k_iterate_merit<T, Sys, HASQR>>(lds, s, c, a, steps, n_obs, box, (T)model.box.q1);
+    }
     case WAVE_PLAIN:
       break;
   }

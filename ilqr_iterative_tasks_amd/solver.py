@@ -158,8 +158,12 @@ class BatchedILQR:
         (K = 2 ... 8 obstacle records per problem on k_iterate_obs: `obs` is then [B, K, 6] and
         shape("obs", B) says so; 0 off), "wave_chain" (1: solve_chained runs on k_chain_box, one
         wavefront per chain, where the speculative chain kernel is not built - a state box,
-        "obstacles", "line_search", stage weights, quad12, ...; 0 off).  All but "wave_tail",
-        "group_lanes", "line_search" and "obstacles" leave the results bit-identical."""
+        "obstacles", "line_search", stage weights, quad12, ...; 0 off), "barrier_cost" (1: the
+        line search, the accept / reject step and the convergence test see the merit J = c + P, the
+        barrier-free cost plus the barriers of the inputs, the records and the state box, on
+        k_iterate_merit; `cost` then returns J; solve_chained refuses; 0 off).  All but
+        "wave_tail", "group_lanes", "line_search", "obstacles" and "barrier_cost" leave the results
+        bit-identical."""
         self._check(self.lib.i2lqr_set_option(self._handle, name.encode(), int(value)))
         if name == "obstacles":
             self.obstacles = int(value) if int(value) > 1 else 1

@@ -398,6 +398,40 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     forced "group_lanes" 8 or 16.  -1 or 0: off (the default: every refusal of
  *                     i2lqr_solve_chained stays).  Any other value is I2LQR_ERR_INVALID; a
  *                     batch-minor / batch-tiled handle answers I2LQR_ERR_UNSUPPORTED to 1.
+ *   "barrier_cost"    1: the cost that decides accept / reject, picks the line search's winner and
+ *                     drives the lamb schedule contains the exponential barriers - NOT the
+ *                     reference's model: there (control/iterative_ilqr.py:43-48) and in every other
+ *                     form of the kernels the barriers enter the backward pass's derivatives only, so
+ *                     the gains descend one function and the accept test looks at another.  With
+ *                     c(X, U) the barrier-free cost (exactly today's, the xtarget / x_terminal quirk
+ *                     of the stage terms kept) the merit is J = c + P with the penalty on the clipped
+ *                     inputs and the rolled-out states
+ *                       P(X, U) = sum_{t<N} sum_{a<m} ctrl_q1 (e^{ctrl_q2 (u_t[a] - u_max[a])}
+ *                                                              + e^{ctrl_q2 (-u_max[a] - u_t[a])})
+ *                               + sum_{t<=N} sum_{records r with r[5] >= 0} obs_q1 e^{obs_q2 h_r(x_t, t)}
+ *                               + sum_{t<=N} sum_{i bounded} box.q1 (e_hi + e_lo)
+ *                     - h_r the obstacle barrier's (the centre moves with index t, index N is the
+ *                     terminal term, P = diag(1 / r[2]^2, 1 / r[3]^2), safety_margin), e_hi / e_lo the
+ *                     state box's (an unbounded side is masked, not computed): the functions whose
+ *                     first derivatives the backward pass uses.  Line search: the winner is
+ *                     argmin_j J_j (NaN never wins, ties go to the smallest j).  Accept iff J_new is
+ *                     finite and J_new < J; the lamb schedule is unchanged.  Converged iff accepted
+ *                     and |(J_new - J) / c| < eps, c the barrier-free cost of the nominal trajectory
+ *                     being replaced (the input barriers alone put a near-constant floor of about
+ *                     N m 2 ctrl_q1 e^{-ctrl_q2 u_max} under J: a test relative to J would stop
+ *                     early).  cost[] returns J of the returned trajectory; a non-finite J at entry
+ *                     ends as status 4.  In fp32 e^{q2 (x - hi)} overflows near q2 (x - hi) = 88: a
+ *                     limit of the option.  The barriers' stiffness is unchanged, so bounds stay as
+ *                     soft in the closed loop as q1, q2 make them.  EVERY call of the handle runs on
+ *                     k_iterate_merit - one problem per wavefront (three plants, both precisions,
+ *                     with or without stage weights), k_iterate_box with this accept step: it
+ *                     composes with "line_search", "obstacles" and the state box (a box that is
+ *                     off and one record are valid).  i2lqr_backward has no accept step and is not
+ *                     concerned.  i2lqr_solve_chained answers I2LQR_ERR_UNSUPPORTED with or without
+ *                     "wave_chain" (the chain kernels have no barrier cost: a launch per chain step
+ *                     instead), and so does a forced "group_lanes" 8 or 16.  -1 or 0: off (the
+ *                     default: nothing changes).  Any other value is I2LQR_ERR_INVALID; a batch-minor
+ *                     / batch-tiled handle answers I2LQR_ERR_UNSUPPORTED to 1.
  *   "stagger"         lane layouts (k_lane_iterate_rows, k_lane_iterate): every second half-thousand
  *                     of workgroups starts value x ~8000 cycles late, so that half of the
  *                     wavefronts stream their gains (forward pass) while the other half computes
@@ -438,7 +472,7 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value);
 int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, double q1, double q2);
 
 /* Name of the kernel i2lqr_iterate (fixed iteration count) launches for a batch of B problems
- * with the handle's current options: "k_iterate", "k_iterate (line search)", "k_iterate (several obstacles)", "k_iterate (state box)", "k_group_iterate", "k_group_iterate (sixteen
+ * with the handle's current options: "k_iterate", "k_iterate (line search)", "k_iterate (several obstacles)", "k_iterate (state box)", "k_iterate (barrier cost)", "k_group_iterate", "k_group_iterate (sixteen
  * lanes)", "k_group_iterate (workspace form)", "k_group_spec", "k_group_spec (sixteen lanes)",
  * "k_quad_iterate", "k_lane_iterate", "k_lane_iterate_pair" (the helper-wavefront form),
  * "k_lane_iterate_rows"; "unsupported" if a forced option cannot be honoured and the launch would
@@ -513,7 +547,9 @@ int i2lqr_solve(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term
  * than 512 chains, a horizon whose three-wavefront buffers do not fit the LDS; a state box,
  * "obstacles", "line_search") unless "wave_chain" is 1 - the chain then runs on k_chain_box, one
  * wavefront per chain, with the same contract for lamb[] -: solve the chain steps one after the
- * other instead (the Python host's HipCandidateSolver.solve_chained does).
+ * other instead (the Python host's HipCandidateSolver.solve_chained does).  With "barrier_cost" on
+ * the answer is I2LQR_ERR_UNSUPPORTED with or without "wave_chain": neither chain kernel has the
+ * barrier cost.
  */
 int i2lqr_solve_chained(i2lqr_handle* h, int64_t chains, int32_t chain_len, void* X, void* U,
                         const void* x_term, void* lamb, const void* obs, void* cost, void* K, void* k,

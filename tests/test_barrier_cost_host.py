@@ -1,0 +1,333 @@
+"""CPU suite of the "barrier_cost" option (include/i2lqr.h): the penalty of
+barrier_cost_reference.py is the function whose derivatives the backward pass uses (the oracle's
+dumped l_x / V_x obstacle terms, state_box_reference.barrier_terms' d1, the dumped l_u), the loop is
+box_reference's without the merit, every run the GPU tests compare meets the conditioning rule, the
+option matters on the termination runs, the closed loop finishes its laps, HipCandidateSolver plumbs
+the option, the header documents it, and the host rules (WaveModel, chain_plan) hold under ASan and
+UBSan."""
+import functools
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import barrier_cost_reference as bc
+import multi_obstacle_reference as mo
+import state_box_reference as sb
+
+ROOT = Path(__file__).resolve().parent.parent
+CSRC = ROOT / "ilqr_iterative_tasks_amd" / "csrc"
+IDS = [f"{c}-{'solve' if i is None else i}-A{A}" for c, i, A in bc.GPU_RUNS]
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(case, n_iters, A=1, merit=True):
+    cfg, host, box = bc.make_case(case)
+    if merit:
+        return bc.merit_reference(cfg, host, box, A, max_iter=n_iters, early_exit=n_iters is None)
+    return sb.box_reference(cfg, host, box, A, max_iter=n_iters, early_exit=n_iters is None)
+
+
+def _central(f, arr, h):
+    """d f / d arr[:, index] for every index, all problems at once (f returns one value per problem)."""
+    g = np.zeros_like(arr)
+    for index in np.ndindex(*arr.shape[1:]):
+        up, dn = arr.copy(), arr.copy()
+        up[(slice(None),) + index] += h
+        dn[(slice(None),) + index] -= h
+        g[(slice(None),) + index] = (f(up) - f(dn)) / (2 * h)
+    return g
+
+
+@pytest.mark.parametrize("case", ["b4_K2", "b6_K2", "quad12"])
+def test_the_penalty_is_what_the_backward_pass_differentiates(case):
+    """Central differences of P (h = 1e-6) against the oracle's dumps.  Bound: the rounding of a
+    central difference, 2 dP / (2 h) with dP <= (log2 T + 3) eps max|P| - T = (N + 1) (2 m + 2 n + K)
+    terms, each an exponential good to an ulp, summed pairwise by NumPy in three stages - plus the
+    truncation h^2 |f'''| / 6 <= 1e-6 |f'| (|f'''| / |f'| <= rate^2 with rate = q2 <= 20 for the
+    box and obs_q2 |h'| of a few tens for a record).  A wrong factor or sign errs by |f'| itself: the
+    largest derivative of every family is asserted to stand at least 100 times above the bound
+    (but for quad12's record, which lies far from the hovering path: its terms are below 1e-30)."""
+    from oracle import oracle as orc
+    cfg, host, box = bc.make_case(case)
+    assert not any(cfg.R)  # (R = 0: the dumped l_u is the input barrier's derivative alone)
+    B, n, m, N, h = host["X"].shape[0], cfg.n, cfg.m, cfg.N, 1e-6
+    obs = mo.records(host["obs"], B)
+    X, U, _ = orc.rollout_batch(cfg, host["X"], host["U"], host["x_term"])
+    # move the inputs off zero, inside the input box, so that l_u is not the symmetric point's zero
+    rng = np.random.default_rng(5)
+    u_max = np.array(cfg.u_max[:m])[None, :, None]
+    U = rng.uniform(-0.9, 0.9, U.shape) * u_max
+    X, U, _ = orc.rollout_batch(cfg, host["X"], U, host["x_term"])
+    P = bc.penalty(cfg, X, U, obs, box)
+    T = (N + 1) * (2 * m + 2 * n + obs.shape[1])
+    bound = (np.log2(T) + 3) * np.finfo(float).eps * np.abs(P).max() / h
+    # the oracle's dumps: obstacle terms as (with the record) - (without), l_u without a record
+    lx, Vx, lu = np.zeros((B, n, N)), np.zeros((B, n)), np.zeros((B, m, N))
+    for b in range(B):
+        _, _, d0 = orc.backward(cfg, X[b], U[b], host["x_term"][b], host["lamb"][b], None, dump=True)
+        lu[b] = d0["l_u"]
+        for rec in obs[b]:
+            if rec[5] >= 0:
+                _, _, dr = orc.backward(cfg, X[b], U[b], host["x_term"][b], host["lamb"][b], rec, dump=True)
+                lx[b] += dr["l_x"] - d0["l_x"]
+                Vx[b] += dr["V_x"] - d0["V_x"]
+    want_obs = np.concatenate([lx, Vx[:, :, None]], axis=2)
+    got_obs = _central(lambda Xp: bc.penalty(cfg, Xp, U, obs, None), X, h)
+    want_box = sb.barrier_terms(box, X)[0]
+    got_box = _central(lambda Xp: bc.penalty(cfg, Xp, U, None, box), X, h)
+    got_u = _central(lambda Up: bc.penalty(cfg, X, Up, obs, box), U, h)
+    for name, got, want in (("records: l_x, V_x", got_obs, want_obs), ("box: d1", got_box, want_box),
+                            ("inputs: l_u", got_u, lu)):
+        err = np.abs(got - want)
+        tol = bound + 1e-6 * np.abs(want)
+        print(f"{case} {name}: largest error {err.max():.3g}, bound {bound:.3g}, largest derivative "
+              f"{np.abs(want).max():.3g}")
+        assert (err <= tol).all(), name
+        if not (case == "quad12" and name.startswith("records")):
+            assert np.abs(want).max() >= 100 * bound, name
+
+
+@pytest.mark.parametrize("case,n_iters,A", [("b4", 3, 1), ("b6_K2", 3, 4), ("b4_weights", None, 1)])
+def test_without_the_merit_the_loop_is_box_references(case, n_iters, A):
+    cfg, host, box = bc.make_case(case)
+    mine = bc.merit_reference(cfg, host, box, A, max_iter=n_iters, early_exit=n_iters is None,
+                              merit=False)
+    ref = _reference(case, n_iters, A, merit=False)
+    for key in ref:
+        assert np.array_equal(ref[key], mine[key]), key
+
+
+@pytest.mark.parametrize("case,n_iters,A", bc.GPU_RUNS, ids=IDS)
+def test_gpu_runs_meet_the_conditioning_rule(case, n_iters, A):
+    """A problem is compared on the GPU only if its smallest deciding margin is >= 1e-7 (ten times
+    the 1e-8 allowed on X and U).  A fixed-count run may leave out no problem, a termination run at
+    most 20 %."""
+    margin = _reference(case, n_iters, A)["margin"]
+    out = (margin < bc.MARGIN).mean()
+    print(f"{case}: smallest margin {margin.min():.3g}, {out:.1%} of the problems below {bc.MARGIN}")
+    assert out <= bc.MAX_LEFT_OUT[n_iters is None]
+
+
+def test_the_unboxed_gpu_run_meets_the_conditioning_rule():
+    """test_gpu_barrier_cost.py's run without a box (b4, three iterations) asks for 80 %."""
+    cfg, host = mo.ls_case("b4")
+    margin = bc.merit_reference(cfg, host, None, 1, max_iter=3, early_exit=False)["margin"]
+    print(f"smallest margin {margin.min():.3g}")
+    assert (margin >= bc.MARGIN).mean() >= 0.8
+
+
+@pytest.mark.parametrize("case,n_iters,A", bc.TERMINATION_RUNS,
+                         ids=[f"{c}-A{A}" for c, _, A in bc.TERMINATION_RUNS])
+def test_the_option_matters(case, n_iters, A):
+    """The rule of the sibling suites: the option moves at least 15 % of the problems by more than
+    1e-3 relative (against box_reference, the soft accept test)."""
+    full, soft = _reference(case, None, A), _reference(case, None, A, merit=False)
+    B = len(full["X"])
+    d = (np.abs(full["X"] - soft["X"]).reshape(B, -1).max(axis=1) /
+         np.abs(soft["X"]).reshape(B, -1).max(axis=1))
+    print(f"{case}: the option moves {(d > 1e-3).mean():.0%} of the problems; LAMB_OVERFLOW exits "
+          f"{(soft['status'] == 3).sum()} -> {(full['status'] == 3).sum()}")
+    assert (d > 1e-3).mean() >= 0.15
+
+
+def test_closed_loop_laps_on_the_host():
+    """Config 1 (N = 6, 2 x 8 candidates, chained lamb, the static obstacle), three controlled laps
+    with the option on, with and without the speed-limit box: every lap finishes feasibly, in the
+    golden file's steps and with its top speeds.  (The option does not harden the bound: the laps'
+    top speeds stay where the barrier's stiffness q1 = q2 = 1 puts them.)"""
+    gold = bc.golden_laps()
+    for box, steps_key, top_key in ((None, "steps", "top"), (sb.speed_limit_box(), "steps_box", "top_box")):
+        steps, ego = sb.controlled_laps(bc.MeritCandidateSolver(box))
+        top = sb.top_speeds(ego)
+        print("box" if box is not None else "no box", "lap steps", steps, "top speeds", top)
+        assert all(f.all() for f in ego.diagnostics["feasibility"])
+        assert len(steps) == 4 and max(steps[1:]) < 120  # (a lap that runs out of time has 121 states)
+        assert steps == list(gold[steps_key])
+        np.testing.assert_allclose(top, gold[top_key], rtol=0, atol=1e-6)
+
+
+class _FakeSolver:
+    """Stands in for BatchedILQR: records what HipCandidateSolver asks of its handle."""
+    made = []
+
+    def __init__(self, cfg, device="cuda:0"):
+        self.cfg, self.options, self.box = cfg.copy(), [], None
+        _FakeSolver.made.append(self)
+
+    def set_option(self, name, value):
+        self.options.append((name, value))
+
+    def set_state_box(self, lo, hi, q1, q2):
+        self.box = (lo, hi, q1, q2)
+
+
+def test_candidate_solver_plumbs_the_option(monkeypatch):
+    """(no GPU: the handles are stand-ins)"""
+    from ilqr_iterative_tasks_amd import default_config, solver as solver_mod
+    from ilqr_iterative_tasks_amd.control import StateBox
+    from ilqr_iterative_tasks_amd.control.iterative_ilqr import HipCandidateSolver
+    monkeypatch.setattr(solver_mod, "BatchedILQR", _FakeSolver)
+    _FakeSolver.made = []
+    assert HipCandidateSolver().barrier_cost is False
+    on = HipCandidateSolver(barrier_cost=True)
+    assert on.barrier_cost is True
+    lane = default_config("bicycle4", 6, layout=2)
+    handle = on._solver(lane, 65536)
+    assert handle.cfg.layout == 0  # problem-major, whatever the library recommends for the batch
+    assert ("barrier_cost", 1) in handle.options
+    assert on._solver(lane, 16) is handle and len(_FakeSolver.made) == 1
+    # the option is part of the key; line search, records and a box come with it
+    limit = StateBox([-np.inf, -np.inf, 0, -np.inf], [np.inf, np.inf, 8, np.inf])
+    both = HipCandidateSolver(barrier_cost=True, line_search=4, state_box=limit)
+    handle = both._solver(default_config("bicycle4", 6), 16, n_obs=2)
+    assert [name for name, _ in handle.options] == ["line_search", "obstacles", "barrier_cost"]
+    assert handle.box is not None
+    off = HipCandidateSolver()
+    off._solvers = on._solvers  # the same cache: a handle without the option is another entry
+    cfg0 = default_config("bicycle4", 6)
+    with_option = on._solver(cfg0, None)
+    assert off._solver(cfg0, None) is not with_option
+    with pytest.raises(ValueError, match="barrier_cost.*wave_chain|wave_chain.*barrier_cost"):
+        HipCandidateSolver(barrier_cost=True, wave_chain=True)
+
+
+def test_header_documents_the_option_and_the_kernel_name():
+    hdr = (ROOT / "include" / "i2lqr.h").read_text()
+    assert '"barrier_cost"' in hdr and '"k_iterate (barrier cost)"' in hdr
+    for text in ("J = c + P", "argmin_j J_j", "|(J_new - J) / c| < eps", "cost[] returns J",
+                 "control/iterative_ilqr.py:43-48", "a launch per chain step"):
+        assert text in hdr, text
+    model = (CSRC / "i2lqr_wave_model.hpp").read_text()
+    assert '"k_iterate (barrier cost)"' in model
+    units = subprocess.run(["make", "-s", "-C", str(CSRC), "units"], capture_output=True, text=True,
+                           check=True).stdout.split()
+    assert "i2lqr_wave_merit" in units
+
+
+PROGRAM = r"""
+#include "i2lqr_column_plan.hpp"
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <initializer_list>
+
+using namespace i2lqr;
+
+static int bad = 0;
+#define CHECK(cond)                                              \
+  do {                                                           \
+    if (!(cond)) {                                               \
+      std::printf("FAILED line %d: %s\n", __LINE__, #cond);      \
+      bad++;                                                     \
+    }                                                            \
+  } while (0)
+
+static WaveModel model(int ls, int obs, bool box, bool merit) {
+  WaveModel m;
+  m.ls = ls;
+  m.obs = obs;
+  if (box) {
+    m.box.hi[0] = 2.5;
+    m.box.m_hi = 1u;
+  }
+  m.barrier_cost = merit;
+  return m;
+}
+
+int main() {
+  // the barrier cost sits above the box in the precedence order, whatever else is on
+  for (int ls : {0, 4})
+    for (int obs : {0, 3})
+      for (bool box : {false, true}) {
+        const WaveModel m = model(ls, obs, box, true);
+        CHECK(m.form() == WAVE_MERIT && m.form(false) == WAVE_MERIT);
+        CHECK(m.form(true) == WAVE_BOX);
+        CHECK(!std::strcmp(wave_kernel_name(m.form()), "k_iterate (barrier cost)"));
+        CHECK(m.steps() == (ls ? ls : 1) && m.records() == (obs ? obs : 1));
+        // a call without a forward pass has no accept step: the option does not concern it
+        CHECK(m.without_line_search().form() == model(0, obs, box, false).form());
+        CHECK(!m.without_line_search().barrier_cost);
+      }
+  CHECK(WAVE_MERIT > WAVE_BOX);
+  CHECK(!WaveModel().barrier_cost && WaveModel().form() == WAVE_PLAIN);
+  CHECK(model(4, 3, true, false).form() == WAVE_BOX);
+  // the LDS behind the slice is the box form's: 6 K + 2 n (N + 1) + 2 n words, box on or off
+  CHECK(model(0, 2, true, true).extra_lds_bytes(WAVE_MERIT, 4, 6, 8) == 608);
+  CHECK(model(0, 0, false, true).extra_lds_bytes(WAVE_MERIT, 12, 20, 4) == 2136);
+  CHECK(model(0, 0, false, true).extra_lds_bytes(WAVE_MERIT, 4, 6, 8) ==
+        model(0, 0, true, false).extra_lds_bytes(WAVE_BOX, 4, 6, 8));
+  CHECK(std::strstr(wave_phrase(WAVE_MERIT), "\"barrier_cost\""));
+  CHECK(std::strstr(wave_lack_phrase(WAVE_MERIT), "\"barrier_cost\""));
+
+  // column_kernel: every call on the opt-in form; "group_lanes" 8 / 16 refused by name
+  const DeviceGeometry g;
+  ColumnFit f;
+  f.plant = ColumnFit::BICYCLE;
+  f.problem_major = true;
+  f.n = 6; f.N = 20;
+  f.lds_wave = 8736; f.lds_group8 = 77472; f.lds_group16 = 36384;
+  f.lds_spec8x2 = 114912; f.lds_spec8x3 = 152864; f.lds_spec16x2 = 54528; f.lds_spec16x3 = 71968;
+  ColumnTune t;
+  for (int64_t B : {(int64_t)1, (int64_t)4096, (int64_t)65536})
+    for (bool solve : {false, true}) {
+      const ColumnChoice c = column_kernel(g, f, t, WAVE_MERIT, -1, B, solve);
+      CHECK(c.kernel == K_WAVE_OPT);
+      CHECK(!std::strcmp(column_kernel_name(c.kernel, WAVE_MERIT), "k_iterate (barrier cost)"));
+    }
+  for (int lanes : {8, 16}) {
+    ColumnTune pin;
+    pin.opt_group = lanes;
+    const ColumnChoice c = column_kernel(g, f, pin, WAVE_MERIT, -1, 64, false);
+    CHECK(c.kernel == K_INVALID && std::strstr(c.why, "\"barrier_cost\"") &&
+          std::strstr(c.why, "\"group_lanes\""));
+  }
+  {
+    ColumnTune pin;
+    pin.opt_group = 64;
+    CHECK(column_kernel(g, f, pin, WAVE_MERIT, -1, 64, false).kernel == K_WAVE_OPT);
+  }
+  // the LDS need of a call is the box form's
+  CHECK(wave_lds_need(f, model(0, 2, false, true), false) == 8736 + (12 + 2 * 6 * 21 + 12) * 8);
+
+  // chain_plan: refused with and without "wave_chain", whatever else would run; the text says why
+  // and points to a launch per chain step
+  for (int wc : {0, 1})
+    for (int64_t chains : {(int64_t)1, (int64_t)8, (int64_t)513}) {
+      ColumnTune c;
+      c.opt_wave_chain = wc;
+      const ChainPlan p = chain_plan(g, f, c, WAVE_MERIT, -1, chains);
+      CHECK(p.kind == ChainPlan::REFUSED);
+      CHECK(std::strstr(p.why, "\"barrier_cost\"") && std::strstr(p.why, "\"wave_chain\"") &&
+            std::strstr(p.why, "a launch per chain step"));
+    }
+  {  // ... and the other forms run as before
+    ColumnTune c;
+    CHECK(chain_plan(g, f, c, WAVE_PLAIN, -1, 8).kind == ChainPlan::SPEC);
+    c.opt_wave_chain = 1;
+    CHECK(chain_plan(g, f, c, WAVE_BOX, -1, 8).kind == ChainPlan::WAVE);
+  }
+
+  std::printf("%d failed\n", bad);
+  return bad ? 1 : 0;
+}
+"""
+
+
+def test_host_rules_against_literals_under_sanitizers(tmp_path):
+    cxx = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    src = tmp_path / "barrier_cost_rules.cpp"
+    src.write_text(PROGRAM)
+    exe = tmp_path / "barrier_cost_rules"
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
+                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    print(run.stdout, run.stderr)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "0 failed" in run.stdout

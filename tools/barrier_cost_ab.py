@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""A/B of the "barrier_cost" option (include/i2lqr.h) against k_iterate_box in ONE process:
+
+    barrier_cost_ab.py [--out FILE] [--reps R] [--variant-lib PATH --variant-name TEXT]
+
+For bicycle4 N = 6, bicycle6 N = 20 and quad12 N = 50 (fp64, 256 problems, one obstacle record per
+problem, one bounded state component), with 1 and 4 step sizes: k_iterate_box and k_iterate_merit
+on handles of the same shape - time per 10 fixed iterations (device events, median over the
+repetitions, the variants alternating inside every repetition, every launch on its own copy of the
+batch) and the share of the 10 iterations that were accepted.  --variant-lib adds k_iterate_merit of
+another build of the library (make variant ...) as a third variant.
+Then, for the termination runs of tests/barrier_cost_reference.py (and b4_weights), the share of
+LAMB_OVERFLOW exits and the mean final J with the option off and on.
+Writes JSON (default profiles/barrier_cost_ab.json).  Not part of bench.py, not a test.
+"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+import numpy as np
+import torch
+
+from ilqr_iterative_tasks_amd import BatchedILQR, default_config, workloads
+from obstacles_ab import device_sets, timed
+
+
+def configurations():
+    # (name, config, problems, bounded component, (lo, hi), q2)
+    return [("bicycle4 N=6 fp64", default_config("bicycle4", 6, "f64"), 256, 2, (0.0, 10.0), 1.0),
+            ("bicycle6 N=20 fp64", default_config("bicycle6", 20, "f64", dt=0.25), 256, 2, (0.0, 10.0), 1.0),
+            ("quad12 N=50 fp64", default_config("quad12", 50, "f64", dt=0.02), 256, 2, (-0.05, 0.05), 20.0)]
+
+
+def make_solver(cfg, steps, comp, bound, q2, merit, lib_path=None):
+    solver = BatchedILQR(cfg, lib_path=lib_path)
+    lo, hi = np.full(cfg.n, -np.inf), np.full(cfg.n, np.inf)
+    lo[comp], hi[comp] = bound
+    solver.set_state_box(lo, hi, 1.0, q2)
+    if steps > 1:
+        solver.set_option("line_search", steps)
+    if merit:
+        solver.set_option("barrier_cost", 1)
+    return solver
+
+
+def measure(cfg, B, steps, comp, bound, q2, reps, variant_lib):
+    host = workloads.make_batch(cfg, B)
+    obs = np.ascontiguousarray(workloads.obstacles_on_path(host, 2)[:, 0])
+    solvers = {"box": make_solver(cfg, steps, comp, bound, q2, False),
+               "merit": make_solver(cfg, steps, comp, bound, q2, True)}
+    if variant_lib:
+        solvers["merit (variant library)"] = make_solver(cfg, steps, comp, bound, q2, True, variant_lib)
+    sets = {v: device_sets(s, host, obs, reps + 1) for v, s in solvers.items()}
+    ms = {v: [] for v in solvers}
+    for r in range(reps + 1):  # (repetition 0 warms every variant up)
+        for v in solvers:
+            ms[v].append(timed(lambda: solvers[v].iterate(sets[v][r], 10)))
+    rows = {}
+    for v, s in solvers.items():
+        t = np.array(ms[v][1:])
+        j = np.rint(np.log(sets[v][-1]["lamb"].cpu().numpy()) / np.log(cfg.lamb_factor))
+        rows[v] = dict(kernel=s.iterate_kernel(B), iterate10_ms_median=float(np.median(t)),
+                       iterate10_ms_min=float(t.min()), iterate10_ms_max=float(t.max()),
+                       accepted_share=float(((10 - j) / 2).mean() / 10))
+    for v in rows:
+        rows[v]["iterate10_over_k_iterate_box"] = (rows[v]["iterate10_ms_median"] /
+                                                   rows["box"]["iterate10_ms_median"])
+    for s in solvers.values():
+        s.close()
+    return rows
+
+
+def termination(case, A):
+    """LAMB_OVERFLOW exits and the mean final J of a problem set solved to termination, the option
+    off (J computed on the host from the returned trajectory) and on."""
+    import barrier_cost_reference as bc
+    from helpers import dev_batch, to_host
+    cfg, host, box = bc.make_case(case)
+    out = {}
+    for merit in (False, True):
+        solver = BatchedILQR(cfg)
+        if host["obs"].ndim == 3:
+            solver.set_option("obstacles", host["obs"].shape[1])
+        if A > 1:
+            solver.set_option("line_search", A)
+        solver.set_state_box(box.lo, box.hi, box.q1, box.q2)
+        solver.set_option("barrier_cost", int(merit))
+        buf = solver.solve(dev_batch(solver, host))
+        X, U = to_host(solver, buf["X"]), to_host(solver, buf["U"])
+        cost = buf["cost"].cpu().numpy()
+        J = cost if merit else cost + bc.penalty(cfg, X, U, host["obs"], box)
+        out["merit" if merit else "soft"] = dict(
+            lamb_overflow=int((buf["status"].cpu().numpy() == 3).sum()), mean_final_J=float(J.mean()),
+            mean_iters=float(buf["iters"].cpu().numpy().mean()))
+        out.setdefault("J", []).append(J)
+        solver.close()
+    soft, merit = out.pop("J")
+    out["problems"] = int(len(soft))
+    out["J_lower_share"] = float((merit < soft * (1 - 1e-6)).mean())
+    out["J_higher_share"] = float((merit > soft * (1 + 1e-6)).mean())
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "barrier_cost_ab.json"))
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--variant-lib", default=None)
+    ap.add_argument("--variant-name", default=None, help="what the variant library is, for the JSON")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("barrier_cost_ab.py needs a HIP device")
+    doc = {"device": torch.cuda.get_device_name(0), "reps": args.reps,
+           "note": "\"box\": k_iterate_box, \"merit\": k_iterate_merit on the same box, record and "
+                   "step sizes; times from device events; J_lower / J_higher: the option's final J "
+                   "against the soft run's by more than 1e-6 relative",
+           "variant_lib": args.variant_name if args.variant_lib else None, "configurations": [], "termination": []}
+    for name, cfg, B, comp, bound, q2 in configurations():
+        for steps in (1, 4):
+            rows = measure(cfg, B, steps, comp, bound, q2, args.reps, args.variant_lib)
+            doc["configurations"].append(dict(name=name, B=B, steps=steps, variants=rows))
+            for v, row in rows.items():
+                print(f"{name:20s} B={B:4d} steps={steps} {v:24s}: 10 iterations "
+                      f"{row['iterate10_ms_median']:.4f} ms [{row['iterate10_ms_min']:.4f}, "
+                      f"{row['iterate10_ms_max']:.4f}]  x k_iterate_box "
+                      f"{row['iterate10_over_k_iterate_box']:.3f}  accepted "
+                      f"{row['accepted_share']:.0%}  {row['kernel']}", flush=True)
+    for case, A in (("b4", 1), ("b6", 1), ("b6_K2", 4), ("b4_K2", 1), ("b4_weights", 1)):
+        row = termination(case, A)
+        doc["termination"].append(dict(case=case, steps=A, **row))
+        print(f"{case:12s} steps={A}: {row}", flush=True)
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(doc, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
