@@ -545,6 +545,17 @@ static int refuse_layout(const char* what) {
   return fail(I2LQR_ERR_UNSUPPORTED, "%s is built for the problem-major layout (the "
               "one-problem-per-wavefront kernel)", what);
 }
+// ... but several obstacles and the state box, which a batch-minor / batch-tiled handle of the
+// bicycles takes with "lane_models" 1 (k_lane_iterate_model): 0 if `what` may be switched on
+static int refuse_lane_model(const i2lqr_handle* h, const char* what) {
+  if (problem_major(h)) return I2LQR_OK;
+  if (!h->lane_models) return refuse_layout(what);
+  if (h->cfg.system_id == I2LQR_SYS_QUAD12)
+    return fail(I2LQR_ERR_UNSUPPORTED, "%s with \"lane_models\" is built for the bicycles' "
+                "one-problem-per-lane kernel, not for quad12's row-block kernel "
+                "(k_lane_iterate_rows): use the problem-major layout", what);
+  return I2LQR_OK;
+}
 
 int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   if (!h || !name) return fail(I2LQR_ERR_INVALID, "null handle or option name");
@@ -597,8 +608,23 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
     if (v > I2LQR_MAX_OBSTACLES)
       return fail(I2LQR_ERR_INVALID, "\"obstacles\" is 2 ... %d records per problem, or -1 / 0 / 1 "
                   "(off: one record)", I2LQR_MAX_OBSTACLES);
-    if (v > 1 && !problem_major(h)) return refuse_layout(wave_phrase(WAVE_OBS));
+    if (v > 1)
+      if (int rc = refuse_lane_model(h, wave_phrase(WAVE_OBS))) return rc;
     h->model.obs = v > 1 ? v : 0;
+  }
+  else if (!strcmp(name, "lane_models")) {
+    if (v != -1 && v != 0 && v != 1)
+      return fail(I2LQR_ERR_INVALID, "\"lane_models\" is 1 (on), or -1 / 0 (off)");
+    if (v == 1 && problem_major(h))
+      return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_models\" is built for the batch-minor / batch-tiled "
+                  "layouts (a problem-major handle runs the models on the one-problem-per-wavefront "
+                  "kernels without it)");
+    if (v != 1 && h->lane_models && (h->model.obs > 1 || h->model.box.on()))
+      return fail(I2LQR_ERR_INVALID, "\"lane_models\" cannot be switched off while %s on: %s first",
+                  h->model.box.on() ? "a state box is" : "\"obstacles\" is",
+                  h->model.box.on() ? "clear it (i2lqr_set_state_box with NULL bounds)"
+                                    : "set \"obstacles\" to 1");
+    h->lane_models = v == 1;
   }
   else if (!strcmp(name, "barrier_cost")) {
     if (v != -1 && v != 0 && v != 1)
@@ -646,7 +672,8 @@ int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, dou
       b.m_hi |= 1u << i;
     }
   }
-  if (b.on() && !problem_major(h)) return refuse_layout(wave_phrase(WAVE_BOX));
+  if (b.on())
+    if (int rc = refuse_lane_model(h, wave_phrase(WAVE_BOX))) return rc;
   h->model.box = b;
   return I2LQR_OK;
 }
@@ -655,6 +682,12 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
   if (!h) return "";
   if (h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR) {
     if (h->cfg.system_id == I2LQR_SYS_QUAD12) return "k_lane_iterate_rows";
+    // a model of "lane_models": the launcher's own decision (LaneLaunch::names_model)
+    switch (dispatch(h, [&](auto L) { return L.names_model(h); })) {
+      case 2: return "k_lane_iterate (state box)";
+      case 1: return "k_lane_iterate (several obstacles)";
+      default: break;
+    }
     // the helper-wavefront form (both precisions, with or without stage weights): decided by the
     // launcher's own rules (LaneLaunch::names_pair)
     const auto pair = [&](auto L) { return L.names_pair(h, B, early_exit ? 1 : 0); };

@@ -24,6 +24,9 @@ struct i2lqr_handle {
   i2lqr::ColumnTune col;  // options of the problem-major layout (i2lqr_column_plan.hpp)
   i2lqr::ColumnFit fit;   // what the kernel units know about cfg, filled in i2lqr_create
   i2lqr::WaveModel model;  // one-problem-per-wavefront kernel: "line_search", "obstacles" and the state box (i2lqr_set_state_box), all off by default (i2lqr_wave_model.hpp)
+  // "lane_models" 1: a batch-minor / batch-tiled handle accepts model.obs and model.box and runs them
+  // on k_lane_iterate_model (LaneLaunch::iterate_model); never set on a problem-major handle
+  bool lane_models = false;
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
   // it into its kernel, otherwise the call runs the separate kernels.  The pointer to the call's
   // epilogue is THREAD-LOCAL (t_epi in i2lqr_column_launch.hpp), not handle state: two host threads inside

@@ -264,6 +264,12 @@ constexpr bool kRowsNTAll = I2LQR_ROWS_NT_ALL != 0;  // experiment: every row ac
 #ifndef I2LQR_F32_WAVES
 #define I2LQR_F32_WAVES 1
 #endif
+// LaneWorker::backward's MODEL parameter when no opt-in model is on: every `if constexpr
+// (MODEL::kOn)` of the pass is discarded (the model itself: LaneModelHook, i2lqr_lane_model.hpp)
+struct NoModel {
+  static constexpr bool kOn = false;
+};
+
 template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
   static constexpr int n = Sys::n, m = Sys::m, W = n + m, NT = Sys::NTRIG, NV = Sys::NVAR,
                        NC = Sys::NCONST;
@@ -736,11 +742,17 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
   // same operands as ROLE 0 (the record travels through LDS unchanged): bit-identical.
   static constexpr int kRec = NV + 5 + 2 * m + (HASQR ? n : 0);  // jv, obstacle terms, l_u, l_uu (+ 2 Q dx_t)
   lds_t* rec = nullptr;                        // [2][kRec][64], set by the kernel
-  template <bool FASTBAR = false, bool CK = false, int ROLE = 0>
+  // MODEL (k_lane_iterate_model, ROLE 0 without checkpoints): obstacle records 1 ... K - 1 join the
+  // five words of record 0 in record order, and the state box's d1 / d2 of x_t go to l_x and the
+  // diagonal of l_xx behind the constant and obstacle terms, at every step and in the terminal
+  // block (the order DESIGN.md §3.1 fixes for BoxWorker).
+  template <bool FASTBAR = false, bool CK = false, int ROLE = 0, class MODEL = NoModel>
   __device__ __forceinline__ void backward(const T* X, const T* U, const T (&xT)[n],
                                            const T (&ob)[6], T lamb, T* gK, T* gk, bool k0_out,
-                                           lds_t* seg = nullptr) const {
+                                           lds_t* seg = nullptr, const MODEL& mdl = MODEL()) const {
     static_assert(!(CK && DEEP), "checkpointed states are built for the fp64 kernels");
+    static_assert(!MODEL::kOn || (ROLE == 0 && !CK && Sys::NBLK == 0),
+                  "the models are built for the plain pass of the bicycles");
     static_assert(ROLE == 0 || (!CK && Sys::NBLK == 0),
                   "the helper form is built for the plain pass of the bicycles");
     if constexpr (Sys::NBLK > 0) {
@@ -792,6 +804,7 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
 #pragma unroll
       for (int i = 0; i < n; i++) xN[i] = CK ? seg_at(last_len, i) : at(X, rx(i, N));
       obstacle(ob, ob_pa, ob_pb, xN[0], xN[1], N, o);
+      if constexpr (MODEL::kOn) mdl.more_obstacles(*this, ob[5] >= T(0), xN[0], xN[1], N, o);
 #pragma unroll
       for (int i = 0; i < n; i++) {
         T vx = T(0);
@@ -804,6 +817,17 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
       }
       Va[0][0] += o[2]; Va[0][1] += o[3]; Va[1][0] += o[3]; Va[1][1] += o[4];
       Va[0][n] += o[0]; Va[1][n] += o[1];
+      if constexpr (MODEL::kOn) {
+        if (mdl.box_on()) {
+          T d1[n], d2[n];
+          mdl.box_terms(xN, d1, d2);
+#pragma unroll
+          for (int i = 0; i < n; i++) {
+            Va[i][i] += d2[i];
+            Va[i][n] += d1[i];
+          }
+        }
+      }
     }
     // Software pipeline: the trajectory inputs of a step are consumed at its start (Jacobian
     // entries, barrier terms); the loads of step t-1 are then issued into the same registers, so
@@ -827,11 +851,16 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
       T jv[NV], o[5], tr[NT];
       T lu[m], luu[m];
       T lxq[n];  // 2Q dX[:, t]: control/ilqr_helper.py:29
+      [[maybe_unused]] T bd1[MODEL::kOn ? n : 1], bd2[MODEL::kOn ? n : 1];  // MODEL: the box's d1, d2 of x_t
       STAMP_BEGIN();
       if constexpr (ROLE != 1) {
       Sys::trig(xe, tr);  // the same values the rollout used for the dynamics of step t+1
       Sys::jac_var(c, xe, u, tr, jv);
       obstacle(ob, ob_pa, ob_pb, xp[0], xp[1], t, o);
+      if constexpr (MODEL::kOn) {
+        mdl.more_obstacles(*this, ob[5] >= T(0), xp[0], xp[1], t, o);
+        mdl.box_terms(xp, bd1, bd2);  // (a box that is off: zeros, and no term is added below)
+      }
       // input barrier, add_control_constraint(): control/ilqr_helper.py:83-103
       //   l_u = q1 q2 (e_hi - e_lo),  l_uu = q1 q2^2 (e_hi + e_lo),
       //   e_hi = exp(q2 (u - u_max)),  e_lo = exp(q2 (-u_max - u)).
@@ -946,6 +975,11 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
             if constexpr (a < n) {
               if constexpr (HASQR) l = T(2) * c.Q[a * n + bcol];
               if constexpr (a < 2 && bcol < 2) l += o[2 + a + bcol];
+              if constexpr (MODEL::kOn) {
+                if constexpr (a == bcol) {
+                  if (mdl.box_on()) l += bd2[a];
+                }
+              }
               Qa[a][bcol] = l + acc;
             } else if constexpr (bcol < n) {
               G[a - n][bcol] = acc;
@@ -959,6 +993,9 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
         if constexpr (a < n) {
           T l = lxq[a];
           if constexpr (a < 2) l += o[a];
+          if constexpr (MODEL::kOn) {
+            if (mdl.box_on()) l += bd1[a];
+          }
           Qa[a][n] = l + t1[n];
         } else {
           G[a - n][n] = lu[a - n] + t1[n];

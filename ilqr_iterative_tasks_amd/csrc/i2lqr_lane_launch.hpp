@@ -14,6 +14,7 @@
 #include "i2lqr_host.hpp"
 #include "i2lqr_kernels.h"
 #include "i2lqr_lane12.h"
+#include "i2lqr_lane_model.hpp"
 #include "i2lqr_lane_plan.hpp"
 
 // the launches below are recorded by the dry-run build (empty unless -DI2LQR_DRY_RUN: the ASan build)
@@ -303,7 +304,50 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     return I2LQR_OK;
   }
 
+  // The opt-in models of the handle ("lane_models" 1: the records and the box h->model keeps; a lane
+  // handle without it never holds either): what iterate() launches and what the names report.
+  static LaneModel model(const i2lqr_handle* h) {
+    return LaneModel{h->model.records(), h->model.box.on()};
+  }
+  // 0: no model is on; 1: several obstacles; 2: the state box (it takes precedence, as on the
+  // one-problem-per-wavefront side) - i2lqr_iterate_kernel / i2lqr_solve_kernel
+  static int names_model(const i2lqr_handle* h) {
+    const LaneModel md = model(h);
+    return !md.on() ? 0 : md.box ? 2 : 1;
+  }
+  // i2lqr_iterate / i2lqr_solve with a model on: ONE launch of k_lane_iterate_model whatever the
+  // batch (a solve runs with early exit; "helper_wavefront", "checkpoint_states", "state_buffers" and
+  // i2lqr_set_compaction have no effect)
+  static int iterate_model(i2lqr_handle* h, const SolveIO& io, const LaneModel& md, hipStream_t s) {
+    if constexpr (Sys::NBLK > 0) {
+      return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_models\" is built for the bicycles' "
+                  "one-problem-per-lane kernel, not for the row-block kernel of this plant "
+                  "(k_lane_iterate_rows): use the problem-major layout");
+    } else {
+      if (int rc = need_ws(h, io.B)) return rc;
+      const LaneShape sh = shape(h);
+      const LaneModelPlan p = lane_model_plan(h->geo, sh, h->lane, md, io.B, io.early_exit != 0);
+      if (!p.fits)
+        return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_models\": %d obstacle records take %zu B of LDS per "
+                    "wavefront beside the %d B of k_0, a workgroup of this device gets %zu B",
+                    md.records, p.model_bytes, sh.k0_bytes(), h->geo.default_dyn_lds);
+      const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
+      LaneArgs<T> a = lane_args(h, io.B, p.o);
+      set_io(a, io.n_iters, io.early_exit, user_set(io));
+      a.max_total = io.n_iters;
+      const BoxCfg<T, n> box = make_box_cfg<T, n>(h->model.box);
+      with_weights(c.flags, [&](auto W) {
+        grow_lds(h->geo, &k_lane_iterate_model<T, Sys, W, TILED>, sh, a, grid(io.B), p.model_bytes);
+        hipLaunchKernelGGL((k_lane_iterate_model<T, Sys, W, TILED>), dim3(grid(io.B)), dim3(64),
+                           lane_lds(sh, a) + p.model_bytes, s, c, a, md.records, box);
+      });
+      HIP_TRY(hipGetLastError());
+      return I2LQR_OK;
+    }
+  }
+
   static int iterate(i2lqr_handle* h, const SolveIO& io, hipStream_t s) {
+    if (const LaneModel md = model(h); md.on()) return iterate_model(h, io, md, s);
     const LaneShape sh = shape(h);
     const bool solve = io.early_exit && io.n_iters == h->cfg.max_iter;
     if (solve && chunked(h->geo, sh, h->lane, io.B)) return solve_compacting(h, io, s);

@@ -169,6 +169,47 @@ inline LaneOptions lane_options(const DeviceGeometry& g, const LaneShape& s, con
   return o;
 }
 
+// The opt-in models of a lane handle ("lane_models" 1; k_lane_iterate_model, i2lqr_lane_model.hpp):
+// `records` obstacle records per problem and the state box, both in the backward pass's derivatives.
+struct LaneModel {
+  int records = 1;   // "obstacles": 2 ... I2LQR_MAX_OBSTACLES; 1: off
+  bool box = false;  // i2lqr_set_state_box with a finite bound
+  bool on() const { return records > 1 || box; }
+};
+// LDS of a model launch behind the gain steps and k_0: records 1 ... K - 1 of 64 lanes, six words
+// each, staged once per launch (record 0 stays in registers as in k_lane_iterate; the box is a
+// by-value kernel argument and takes none)
+inline size_t lane_model_bytes(const LaneShape& s, const LaneModel& md) {
+  return md.records > 1 ? (size_t)64 * 6 * (size_t)(md.records - 1) * (size_t)s.word : 0;
+}
+// A model launch: k_lane_iterate's one-wavefront form, states not checkpointed, i2lqr_solve as ONE
+// launch with early exit whatever the batch (k_lane_compact and the tail kernels have no models).
+// The records take the place of LDS-resident gain steps.
+struct LaneModelPlan {
+  LaneOptions o;
+  bool pair, chunked;  // always false: the helper-wavefront form and the chunked solve have no models
+  size_t model_bytes;
+  size_t lds;   // dynamic LDS the launch asks for before grown_lds_steps(): gain steps + k_0 + records
+  bool fits;    // k_0 and the records fit the dynamic LDS a workgroup gets without asking for more
+};
+inline LaneModelPlan lane_model_plan(const DeviceGeometry& g, const LaneShape& s, const LaneTune& t,
+                                     const LaneModel& md, int64_t B, bool solve) {
+  LaneModelPlan p;
+  LaneTune tm = t;
+  tm.opt_ckpt = 0;
+  tm.opt_pair = 0;
+  p.o = lane_options(g, s, tm, B, solve);
+  p.model_bytes = lane_model_bytes(s, md);
+  const long room = (long)g.lds_per_simd_wave() - (long)s.k0_bytes() - (long)p.model_bytes;
+  const int steps = room > 0 ? (int)(room / s.step_bytes()) : 0;
+  if (p.o.lds_steps > steps) p.o.lds_steps = steps;
+  p.pair = use_pair(g, s, p.o, B, tm.opt_pair);
+  p.chunked = false;
+  p.lds = lane_lds(s, p.o) + p.model_bytes;
+  p.fits = (size_t)s.k0_bytes() + p.model_bytes <= g.default_dyn_lds;
+  return p;
+}
+
 // Workspace (byte offsets from the registered base) for B problems: candidate inputs + gains
 // scratch + the second state buffer of the helper-wavefront form (every call), and for the chunked
 // solve two compacted work sets, scratch iters / status and one counter per round.  ONE table:

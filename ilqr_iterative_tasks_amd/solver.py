@@ -161,9 +161,13 @@ class BatchedILQR:
         "obstacles", "line_search", stage weights, quad12, ...; 0 off), "barrier_cost" (1: the
         line search, the accept / reject step and the convergence test see the merit J = c + P, the
         barrier-free cost plus the barriers of the inputs, the records and the state box, on
-        k_iterate_merit; `cost` then returns J; solve_chained refuses; 0 off).  All but
-        "wave_tail", "group_lanes", "line_search", "obstacles" and "barrier_cost" leave the results
-        bit-identical."""
+        k_iterate_merit; `cost` then returns J; solve_chained refuses; 0 off).  Lane layouts of the
+        bicycles: "lane_models" (1: the solver accepts "obstacles" 2 ... 8 and set_state_box() and runs
+        them on k_lane_iterate_model, one problem per lane; `obs` is then [6, K, B] batch-minor /
+        [B/64, 6, K, 64] batch-tiled, which shape("obs", B) and to_native() of a [B, K, 6] tensor give;
+        solve() is then a single launch whatever set_compaction() says; 0 off, refused while a
+        model is on).  All but "wave_tail", "group_lanes", "line_search", "obstacles" and
+        "barrier_cost" leave the results bit-identical."""
         self._check(self.lib.i2lqr_set_option(self._handle, name.encode(), int(value)))
         if name == "obstacles":
             self.obstacles = int(value) if int(value) > 1 else 1
@@ -175,7 +179,9 @@ class BatchedILQR:
         q1 exp(q2 (lo - x)) enters the backward pass's derivatives (not the accept / reject cost: the
         bound is soft).  While a bound is finite every call runs on k_iterate_box, which composes
         with "obstacles" and "line_search"; set_state_box() with no finite bound switches it off
-        (today's kernels, bit for bit).  `state_box` holds (lo, hi, q1, q2) while it is on."""
+        (today's kernels, bit for bit).  A batch-minor / batch-tiled solver of the bicycles takes the
+        box after set_option("lane_models", 1) and runs it on k_lane_iterate_model.  `state_box`
+        holds (lo, hi, q1, q2) while it is on."""
         import numpy as np
         if lo is None and hi is None:
             self._check(self.lib.i2lqr_set_state_box(self._handle, None, None, float(q1), float(q2)))

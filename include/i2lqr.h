@@ -29,6 +29,9 @@
  *        X[B/64][N+1][n][64]  U[B/64][N][m][64]  K[B/64][N][m][n][64]  k[B/64][N][m][64]
  *        x_term[B/64][n][64]  obs[B/64][6][64];  lamb, cost, iters, status stay flat [B].
  *    B must be a multiple of 64.  Same kernels; every wavefront's rows are contiguous in HBM.
+ *    With K = "obstacles" > 1 records per problem ("lane_models" 1 on these two layouts) record r's
+ *    word q is row q K + r:
+ *        batch-minor  obs[6][K][B]        batch-tiled  obs[B/64][6][K][64]
  *  - obs record = {x, y, width, height, spd, moving_option}; moving_option 0 = static,
  *    1 = moving up (+y), 2 = moving left (-x) (utils/base.py:23-34, control/ilqr_helper.py:34-43);
  *    moving_option < 0 disables the obstacle for that problem (the reference's `obstacle is None`).
@@ -381,7 +384,32 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     "wave_chain" is 1) and a forced "group_lanes" 8 or 16 answer
  *                     I2LQR_ERR_UNSUPPORTED.  -1, 0 or 1: off (the
  *                     default: obs[B][6]).  Any other value is I2LQR_ERR_INVALID; a batch-minor /
- *                     batch-tiled handle answers I2LQR_ERR_UNSUPPORTED to 2 ... 8.
+ *                     batch-tiled handle answers I2LQR_ERR_UNSUPPORTED to 2 ... 8 unless
+ *                     "lane_models" is 1 (below: the same records, on k_lane_iterate_model).
+ *   "lane_models"     batch-minor / batch-tiled handles of the bicycles.  1: the handle accepts
+ *                     "obstacles" 2 ... I2LQR_MAX_OBSTACLES and i2lqr_set_state_box with finite bounds,
+ *                     with the semantics written under those two names, word for word: record-order
+ *                     summation starting from the first enabled record's value, moving_option < 0
+ *                     disables a record, a NULL obs all of them; the box's e_hi / e_lo / d1 / d2 with
+ *                     unbounded sides masked and not computed; barriers in the derivatives only.
+ *                     obs is then obs[6][K][B] (batch-minor) / obs[B/64][6][K][64] (batch-tiled).
+ *                     While a model is on, i2lqr_iterate and i2lqr_solve run k_lane_iterate_model:
+ *                     one problem per lane, one wavefront per workgroup; the records beyond the first
+ *                     are staged in LDS (64 * 6 * (K - 1) words per wavefront) in place of
+ *                     LDS-resident gain steps.  i2lqr_solve is then always a SINGLE launch with early
+ *                     exit: i2lqr_set_compaction is ignored (the compaction and the tail kernels have
+ *                     no models), as are "helper_wavefront", "checkpoint_states" and
+ *                     "state_buffers"; "defer_states", "reroll_nominal", "merge_inputs",
+ *                     "lds_gain_steps" and "stagger" apply and preserve the results bit for bit.
+ *                     i2lqr_iterate_pick takes its unfused form; i2lqr_backward answers
+ *                     I2LQR_ERR_UNSUPPORTED while a model is on.  Still I2LQR_ERR_UNSUPPORTED with
+ *                     "lane_models" 1: "line_search" > 1, "barrier_cost" 1 and "wave_chain" 1 on such
+ *                     a handle, and a model on quad12 (its row-block kernel has none).  With no
+ *                     model set the handle runs what it ran before.  -1 or 0: off (the default);
+ *                     I2LQR_ERR_INVALID while "obstacles" > 1 or a box is on (the message names what
+ *                     to clear first).  Any other value is I2LQR_ERR_INVALID; a problem-major handle
+ *                     answers I2LQR_ERR_UNSUPPORTED to 1 (it has the one-problem-per-wavefront
+ *                     kernels) and accepts 0 / -1.
  *   "wave_chain"      1: where i2lqr_solve_chained would answer I2LQR_ERR_UNSUPPORTED on this
  *                     (problem-major) handle - a state box, "obstacles" > 1, "line_search" > 1, stage
  *                     weights, quad12, "group_lanes" 8 or 64, "speculate" 0, more than 512 chains, a
@@ -468,13 +496,16 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value);
  * "wave_chain" is 1) and a forced "group_lanes" 8 or 16 answer I2LQR_ERR_UNSUPPORTED;
  * i2lqr_iterate_pick takes its unfused form.
  * I2LQR_ERR_INVALID: a NaN bound, lo[i] >= hi[i], q1 <= 0 or q2 <= 0, exactly one pointer NULL.
- * I2LQR_ERR_UNSUPPORTED: a finite bound on a batch-minor / batch-tiled handle. */
+ * I2LQR_ERR_UNSUPPORTED: a finite bound on a batch-minor / batch-tiled handle, unless its
+ * "lane_models" is 1 (the bicycles: the same box on k_lane_iterate_model, see that option). */
 int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, double q1, double q2);
 
 /* Name of the kernel i2lqr_iterate (fixed iteration count) launches for a batch of B problems
  * with the handle's current options: "k_iterate", "k_iterate (line search)", "k_iterate (several obstacles)", "k_iterate (state box)", "k_iterate (barrier cost)", "k_group_iterate", "k_group_iterate (sixteen
  * lanes)", "k_group_iterate (workspace form)", "k_group_spec", "k_group_spec (sixteen lanes)",
  * "k_quad_iterate", "k_lane_iterate", "k_lane_iterate_pair" (the helper-wavefront form),
+ * "k_lane_iterate (several obstacles)", "k_lane_iterate (state box)" (k_lane_iterate_model with
+ * "lane_models" 1: the box takes precedence),
  * "k_lane_iterate_rows"; "unsupported" if a forced option cannot be honoured and the launch would
  * return I2LQR_ERR_UNSUPPORTED: what to look for in a rocprofv3 kernel trace.  The name comes from
  * the launcher's own decision code run on scratch arguments, not from a copy of its conditions.

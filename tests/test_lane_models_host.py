@@ -1,0 +1,231 @@
+"""CPU suite of "lane_models" (include/i2lqr.h): the plan of a model launch (i2lqr_lane_plan.hpp: a
+stand-alone program under AddressSanitizer and UBSan, as test_lane_plan_host.py builds one), the
+header's text, and the conditioning of the two 128-problem sets test_gpu_lane_models.py adds to the
+sets test_obstacles_host.py / test_state_box_host.py already pin."""
+import functools
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import lane_models_cases as lm
+import multi_obstacle_reference as mo
+import state_box_reference as sb
+
+ROOT = Path(__file__).resolve().parent.parent
+CSRC = ROOT / "ilqr_iterative_tasks_amd" / "csrc"
+
+PROGRAM = r"""
+#include "i2lqr_lane_plan.hpp"
+
+#include <cstdio>
+#include <initializer_list>
+
+using namespace i2lqr;
+
+static int bad = 0;
+#define CHECK(cond)                                              \
+  do {                                                           \
+    if (!(cond)) {                                               \
+      if (bad < 40) std::printf("FAILED line %d: %s\n", __LINE__, #cond); \
+      bad++;                                                     \
+    }                                                            \
+  } while (0)
+
+static LaneShape shape(int n, int m, int N, int word, bool weights = false, int max_iter = 150) {
+  return LaneShape{n, m, N, word, false, weights, max_iter};
+}
+
+static void model_launches() {
+  const DeviceGeometry g;  // the MI355X figures
+  const int plants[2][2] = {{4, 2}, {6, 2}};
+  long combos = 0;
+  for (const auto& p : plants)
+    for (int word : {8, 4})
+      for (int N : {1, 20, 64})
+        for (int K : {1, 2, 8})
+          for (bool box : {false, true})
+            for (int64_t B : {(int64_t)1, (int64_t)64, (int64_t)4161, (int64_t)65536})
+              for (bool solve : {false, true})
+                for (int pin : {-1, 0, 1}) {  // "helper_wavefront" / "checkpoint_states" pinned or not
+                  const LaneShape s = shape(p[0], p[1], N, word);
+                  LaneModel md;
+                  md.records = K;
+                  md.box = box;
+                  CHECK(md.on() == (K > 1 || box));
+                  LaneTune t;
+                  t.opt_pair = pin;
+                  t.opt_ckpt = pin;
+                  if (pin == 1) { t.opt_merge = 1; t.opt_reroll = 1; t.opt_defer = 1; }
+                  t.compact_min_batch = 64;  // i2lqr_set_compaction(64): ignored by a model launch
+                  const LaneModelPlan q = lane_model_plan(g, s, t, md, B, solve);
+                  combos++;
+                  CHECK(!q.pair && !q.chunked && q.o.ckpt == 0);
+                  // the records: 6 words of 64 lanes each but the first, which stays in registers
+                  CHECK(q.model_bytes == (size_t)64 * 6 * (size_t)(K - 1) * (size_t)word);
+                  CHECK(q.model_bytes == lane_model_bytes(s, md));
+                  // LDS: gain steps + k_0 + records, within the budget of one wavefront per SIMD
+                  CHECK(q.lds == (size_t)q.o.lds_steps * (size_t)s.step_bytes() + (size_t)s.k0_bytes() +
+                                     q.model_bytes);
+                  CHECK(q.lds == lane_lds(s, q.o) + q.model_bytes);
+                  CHECK(q.lds <= g.lds_per_simd_wave());
+                  CHECK(q.fits);
+                  CHECK(q.o.lds_steps >= 0 && q.o.lds_steps <= (N > 1 ? N - 1 : 0));
+                  // ... and as many gain steps as that budget holds, unless the plain launch keeps fewer
+                  LaneTune plain_t = t;
+                  plain_t.opt_ckpt = 0;
+                  const LaneOptions plain = lane_options(g, s, plain_t, B, solve);
+                  const long room = (long)g.lds_per_simd_wave() - s.k0_bytes() - (long)q.model_bytes;
+                  const int most = (int)(room / s.step_bytes());
+                  CHECK(q.o.lds_steps == (plain.lds_steps < most ? plain.lds_steps : most));
+                  // the scheduling options that apply are the plain launch's
+                  CHECK(q.o.defer == plain.defer && q.o.reroll == plain.reroll &&
+                        q.o.merge == plain.merge && q.o.stagger == plain.stagger &&
+                        q.o.lds_grow == plain.lds_grow);
+                  // growth through `fixed`: the records and k_0 stay inside what the launch asks for
+                  for (unsigned wg : {1u, 256u, 512u, 1024u}) {
+                    const int steps = grown_lds_steps(g, s, q.o, wg, q.model_bytes, g.max_dyn_lds);
+                    LaneOptions grown = q.o;
+                    grown.lds_steps = steps;
+                    CHECK(steps >= q.o.lds_steps && steps <= (N > 1 ? N - 1 : 0));
+                    if (steps > q.o.lds_steps)
+                      CHECK(lane_lds(s, grown) + q.model_bytes + 1024 <= g.max_dyn_lds);
+                  }
+                }
+  CHECK(combos == 2L * 2 * 3 * 3 * 2 * 4 * 2 * 3);
+  {  // literals: fp64, n = 6, m = 2, N = 20
+    const LaneShape f64 = shape(6, 2, 20, 8), f32 = shape(6, 2, 20, 4);
+    const LaneTune autom;
+    LaneModel md;
+    md.records = 8;
+    LaneModelPlan q = lane_model_plan(g, f64, autom, md, 65536, false);
+    CHECK(q.model_bytes == 21504 && q.o.lds_steps == 2 && q.lds == 2u * 7168u + 1024u + 21504u);
+    CHECK(q.o.reroll == 1 && q.o.merge == 1 && q.o.defer == 1 && q.o.stagger == 8);
+    md.records = 2;
+    q = lane_model_plan(g, f64, autom, md, 65536, false);
+    CHECK(q.model_bytes == 3072 && q.o.lds_steps == 4);
+    q = lane_model_plan(g, f64, autom, md, 65536, true);  // a solve: one launch, no re-roll / defer
+    CHECK(q.o.reroll == 0 && q.o.defer == 0 && q.o.lds_steps == 4 && !q.chunked);
+    q = lane_model_plan(g, f32, autom, md, 8192, false);
+    CHECK(q.model_bytes == 1536 && q.o.lds_steps == 9 && !q.pair);
+    md.records = 1;
+    md.box = true;  // the box alone takes no LDS
+    q = lane_model_plan(g, f64, autom, md, 8192, false);
+    CHECK(q.model_bytes == 0 && q.o.lds_steps == 5 && q.lds == 5u * 7168u + 1024u && !q.pair);
+    // a device whose workgroups get too little LDS: the plan says so
+    DeviceGeometry small;
+    small.default_dyn_lds = 16 * 1024;
+    md.records = 8;
+    CHECK(!lane_model_plan(small, f64, autom, md, 64, false).fits);
+    CHECK(lane_model_plan(small, f32, autom, md, 64, false).fits);
+  }
+}
+
+// with no model on the plan is the parent commit's: literals read from it for two shapes
+static void plain_launches_are_unchanged() {
+  const DeviceGeometry g;
+  const LaneTune autom;
+  {
+    const LaneShape s = shape(6, 2, 20, 8);
+    const LaneOptions o = lane_options(g, s, autom, 8192, false);
+    CHECK(o.lds_steps == 5 && o.reroll == 0 && o.merge == 0 && o.ckpt == 0 && o.stagger == 0);
+    CHECK(o.defer == 1 && o.lds_grow == 1 && o.two_max == 64 * 256);
+    CHECK(lane_lds(s, o) == 5u * 7168u + 1024u);
+    CHECK(use_pair(g, s, o, 8192, autom.opt_pair));
+    const LaneOptions f = lane_options(g, s, autom, 65536, false);
+    CHECK(f.reroll == 1 && f.merge == 1 && f.ckpt == 1 && f.lds_steps == 3 && f.stagger == 8);
+    CHECK(lane_lds(s, f) == 3u * 7168u + 1024u + 15360u);
+    CHECK(chunked(g, s, autom, 4096) && !chunked(g, s, autom, 4095));
+  }
+  {
+    const LaneShape s = shape(4, 2, 6, 4);
+    const LaneOptions o = lane_options(g, s, autom, 4161, false);
+    CHECK(o.lds_steps == 5 && o.reroll == 0 && o.merge == 0 && o.ckpt == 0 && o.stagger == 0);
+    CHECK(o.defer == 1 && o.lds_grow == 1);
+    CHECK(s.step_bytes() == 2560 && s.k0_bytes() == 512 && lane_lds(s, o) == 5u * 2560u + 512u);
+    const LaneOptions so = lane_options(g, s, autom, 4161, true);
+    CHECK(so.defer == 0 && so.reroll == 0 && so.lds_steps == 5);
+    CHECK(use_pair(g, s, o, 4161, -1) && !use_pair(g, s, o, 4161, 0));
+    // X, U, x_term, obs (six words: the chunked solve has no models), lamb, cost per work set
+    const LaneWorkspace w = lane_workspace(s, 64);
+    CHECK(w.set[0].lamb - w.set[0].obs == 64 * 4 * 6);
+  }
+}
+
+int main() {
+  model_launches();
+  plain_launches_are_unchanged();
+  std::printf("%d failed\n", bad);
+  return bad ? 1 : 0;
+}
+"""
+
+
+def test_lane_model_plan(tmp_path):
+    cxx = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    src = tmp_path / "lane_model_plan_check.cpp"
+    src.write_text(PROGRAM)
+    exe = tmp_path / "lane_model_plan_check"
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
+                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    print(run.stdout, run.stderr)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "0 failed" in run.stdout
+
+
+def test_header_documents_the_option_and_the_layouts():
+    hdr = (ROOT / "include" / "i2lqr.h").read_text()
+    assert '"lane_models"' in hdr
+    assert "obs[6][K][B]" in hdr and "obs[B/64][6][K][64]" in hdr
+    assert "k_lane_iterate_model" in hdr
+    src = (CSRC / "i2lqr_abi.hip").read_text()
+    assert '"k_lane_iterate (several obstacles)"' in src and '"k_lane_iterate (state box)"' in src
+    units = (CSRC / "Makefile").read_text()
+    assert "i2lqr_lane_model_f64" in units and "i2lqr_lane_model_f32" in units
+
+
+# (set, fixed iterations or None for a solve, with the box): what test_gpu_lane_models.py compares
+# with mo_reference / box_reference on the batch-tiled sets
+TILED_RUNS = [(name, n, boxed) for name in sorted(lm.TILED) for n, boxed in ((6, False), (None, True))]
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name, n_iters, boxed, scale=1.0):
+    cfg, host, box = lm.tiled_case(name)
+    host = dict(host, X=host["X"] * scale)  # (only X[:, :, 0] = x0 is non-zero)
+    return sb.box_reference(cfg, host, box if boxed else None, max_iter=n_iters,
+                            early_exit=n_iters is None)
+
+
+@pytest.mark.parametrize("name,n_iters,boxed", TILED_RUNS,
+                         ids=[f"{c}-{'solve' if n is None else n}-{'box' if b else 'records'}"
+                              for c, n, b in TILED_RUNS])
+def test_tiled_sets_are_well_conditioned(name, n_iters, boxed):
+    """A kernel that differs from the reference by round-off must meet the same accept / reject
+    decisions: they do not move when x0 is scaled by 1 + 1e-13 or 1 - 1e-12."""
+    ref = _reference(name, n_iters, boxed)
+    for scale in (1.0 + 1e-13, 1.0 - 1e-12):
+        per = _reference(name, n_iters, boxed, scale)
+        assert np.array_equal(per["lamb"], ref["lamb"]), scale
+        assert np.array_equal(per["iters"], ref["iters"]), scale
+
+
+@pytest.mark.parametrize("name", sorted(lm.TILED))
+def test_tiled_sets_extra_records_and_box_matter(name):
+    """The sets exercise what they are for: the records beyond the first and the box each move the
+    trajectories of at least a tenth of the problems by more than 1e-6 relative."""
+    cfg, host, box = lm.tiled_case(name)
+    assert host["X"].shape[0] == 128 and host["obs"].shape[1:] == (lm.TILED[name][3], 6)
+    full = _reference(name, 6, False)
+    one = mo.mo_reference(cfg, mo.first_record_only(host), max_iter=6, early_exit=False)
+    boxed = sb.box_reference(cfg, host, box, max_iter=6, early_exit=False)
+    for other in (one, boxed):
+        d = (np.abs(full["X"] - other["X"]).reshape(128, -1).max(axis=1) /
+             np.abs(full["X"]).reshape(128, -1).max(axis=1))
+        assert (d > 1e-6).mean() >= 0.1
