@@ -50,6 +50,8 @@ def dev_batch(solver, host: dict, want_gains=True):
     return buf
 
 
+TOL_SOLVE = 1e-8   # whole ilqr(), fp64 (north_star tolerance; SURVEY.md §8c: G2)
+
 # per-problem status words (include/i2lqr.h)
 ST_RUNNING, ST_CONVERGED, ST_MAX_ITER, ST_LAMB_OVERFLOW, ST_NONFINITE = 0, 1, 2, 3, 4
 # check_solve_outputs: (X, cost) tolerances of the returned X against the oracle's fp64 rollout of
@@ -169,6 +171,22 @@ def problems_from_calls(g, N, n=4, m=2):
                 lamb=np.array(g["lamb_in"], float), obs=np.array(g["obs"], float))
 
 
+def candidate_batch(cfg, x0, x_terms, lamb0, obs_rec, U0=None):
+    """The arguments of HipCandidateSolver.solve() -> problem-major host batch: one problem per row
+    of x_terms, all from x0, the obstacle record(s) obs_rec ([6] or [K, 6], or None) shared by all
+    of them (obs[B, 6] or [B, K, 6], a read-only view)."""
+    x_terms = np.atleast_2d(np.asarray(x_terms, float))
+    B = x_terms.shape[0]
+    X = np.zeros((B, cfg.n, cfg.N + 1))
+    X[:, :, 0] = np.asarray(x0, float)
+    U = np.zeros((B, cfg.m, cfg.N)) if U0 is None else np.asarray(U0, float).reshape(B, cfg.m, cfg.N)
+    obs = None
+    if obs_rec is not None:
+        rec = np.asarray(obs_rec, float)
+        obs = np.broadcast_to(rec, (B,) + rec.shape)
+    return dict(X=X, U=U, x_term=x_terms, lamb=np.asarray(lamb0, float).reshape(B), obs=obs)
+
+
 class OracleCandidateSolver:
     """Test double for control.iterative_ilqr.HipCandidateSolver backed by the CPU oracle — lets
     the host-side controller logic run in the CPU-only suite.  Lives in tests/ on purpose: the
@@ -180,16 +198,12 @@ class OracleCandidateSolver:
 
     def solve(self, cfg, x0, x_terms, lamb0, obs_rec, U0=None):
         from oracle import oracle as orc
-        x_terms = np.atleast_2d(np.asarray(x_terms, float))
-        B = x_terms.shape[0]
-        X = np.zeros((B, cfg.n, cfg.N + 1))
-        X[:, :, 0] = np.asarray(x0, float)
-        U = np.zeros((B, cfg.m, cfg.N)) if U0 is None else np.asarray(U0, float).reshape(
-            B, cfg.m, cfg.N)
-        obs = None if obs_rec is None else np.tile(np.asarray(obs_rec, float), (B, 1))
+        host = candidate_batch(cfg, x0, x_terms, lamb0, obs_rec, U0)
+        B = host["X"].shape[0]
+        obs = None if obs_rec is None else np.ascontiguousarray(host["obs"]).reshape(B, 6)
         self.calls += 1
         self.problems += B
-        return orc.ilqr_batch(cfg, X, U, x_terms, np.asarray(lamb0, float).reshape(B), obs,
+        return orc.ilqr_batch(cfg, host["X"], host["U"], host["x_term"], host["lamb"], obs,
                               want_gains=False)
 
     def sharded_round(self, cfg, x0, x_terms_local, qfun_local, lamb0, exchange, total,

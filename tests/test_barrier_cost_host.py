@@ -1,7 +1,7 @@
-"""CPU suite of the "barrier_cost" option (include/i2lqr.h): the penalty of
-barrier_cost_reference.py is the function whose derivatives the backward pass uses (the oracle's
-dumped l_x / V_x obstacle terms, state_box_reference.barrier_terms' d1, the dumped l_u), the loop is
-box_reference's without the merit, every run the GPU tests compare meets the conditioning rule, the
+"""CPU suite of the "barrier_cost" option (include/i2lqr.h): the penalty of opt_in_reference.py is
+the function whose derivatives the backward pass uses (the oracle's dumped l_x / V_x obstacle terms,
+barrier_terms' d1, the dumped l_u), the loop without the merit and the composition is the oracle's
+ilqr(), every run the GPU tests compare meets the conditioning rule, the
 option matters on the termination runs, the closed loop finishes its laps, HipCandidateSolver plumbs
 the option, the header documents it, and the host rules (WaveModel, chain_plan) hold under ASan and
 UBSan."""
@@ -13,21 +13,22 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import barrier_cost_reference as bc
-import multi_obstacle_reference as mo
-import state_box_reference as sb
+from opt_in_cases import (MARGIN, MAX_LEFT_OUT, MERIT_RUNS, MERIT_TERMINATION_RUNS, make_case,
+                          run_id)
+from opt_in_reference import (OUTPUTS, ReferenceCandidateSolver, barrier_terms, controlled_laps,
+                              first_record_only, golden_laps, penalty, records, reference,
+                              speed_limit_box, top_speeds)
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "ilqr_iterative_tasks_amd" / "csrc"
-IDS = [f"{c}-{'solve' if i is None else i}-A{A}" for c, i, A in bc.GPU_RUNS]
+IDS = [run_id(*run) for run in MERIT_RUNS]
 
 
 @functools.lru_cache(maxsize=None)
 def _reference(case, n_iters, A=1, merit=True):
-    cfg, host, box = bc.make_case(case)
-    if merit:
-        return bc.merit_reference(cfg, host, box, A, max_iter=n_iters, early_exit=n_iters is None)
-    return sb.box_reference(cfg, host, box, A, max_iter=n_iters, early_exit=n_iters is None)
+    cfg, host, box = make_case(case, box=True)
+    return reference(cfg, host, A, box=box, merit=merit, max_iter=n_iters,
+                     early_exit=n_iters is None)
 
 
 def _central(f, arr, h):
@@ -51,17 +52,17 @@ def test_the_penalty_is_what_the_backward_pass_differentiates(case):
     largest derivative of every family is asserted to stand at least 100 times above the bound
     (but for quad12's record, which lies far from the hovering path: its terms are below 1e-30)."""
     from oracle import oracle as orc
-    cfg, host, box = bc.make_case(case)
+    cfg, host, box = make_case(case, box=True)
     assert not any(cfg.R)  # (R = 0: the dumped l_u is the input barrier's derivative alone)
     B, n, m, N, h = host["X"].shape[0], cfg.n, cfg.m, cfg.N, 1e-6
-    obs = mo.records(host["obs"], B)
+    obs = records(host["obs"], B)
     X, U, _ = orc.rollout_batch(cfg, host["X"], host["U"], host["x_term"])
     # move the inputs off zero, inside the input box, so that l_u is not the symmetric point's zero
     rng = np.random.default_rng(5)
     u_max = np.array(cfg.u_max[:m])[None, :, None]
     U = rng.uniform(-0.9, 0.9, U.shape) * u_max
     X, U, _ = orc.rollout_batch(cfg, host["X"], U, host["x_term"])
-    P = bc.penalty(cfg, X, U, obs, box)
+    P = penalty(cfg, X, U, obs, box)
     T = (N + 1) * (2 * m + 2 * n + obs.shape[1])
     bound = (np.log2(T) + 3) * np.finfo(float).eps * np.abs(P).max() / h
     # the oracle's dumps: obstacle terms as (with the record) - (without), l_u without a record
@@ -75,10 +76,10 @@ def test_the_penalty_is_what_the_backward_pass_differentiates(case):
                 lx[b] += dr["l_x"] - d0["l_x"]
                 Vx[b] += dr["V_x"] - d0["V_x"]
     want_obs = np.concatenate([lx, Vx[:, :, None]], axis=2)
-    got_obs = _central(lambda Xp: bc.penalty(cfg, Xp, U, obs, None), X, h)
-    want_box = sb.barrier_terms(box, X)[0]
-    got_box = _central(lambda Xp: bc.penalty(cfg, Xp, U, None, box), X, h)
-    got_u = _central(lambda Up: bc.penalty(cfg, X, Up, obs, box), U, h)
+    got_obs = _central(lambda Xp: penalty(cfg, Xp, U, obs, None), X, h)
+    want_box = barrier_terms(box, X)[0]
+    got_box = _central(lambda Xp: penalty(cfg, Xp, U, None, box), X, h)
+    got_u = _central(lambda Up: penalty(cfg, X, Up, obs, box), U, h)
     for name, got, want in (("records: l_x, V_x", got_obs, want_obs), ("box: d1", got_box, want_box),
                             ("inputs: l_u", got_u, lu)):
         err = np.abs(got - want)
@@ -91,39 +92,47 @@ def test_the_penalty_is_what_the_backward_pass_differentiates(case):
 
 
 @pytest.mark.parametrize("case,n_iters,A", [("b4", 3, 1), ("b6_K2", 3, 4), ("b4_weights", None, 1)])
-def test_without_the_merit_the_loop_is_box_references(case, n_iters, A):
-    cfg, host, box = bc.make_case(case)
-    mine = bc.merit_reference(cfg, host, box, A, max_iter=n_iters, early_exit=n_iters is None,
-                              merit=False)
-    ref = _reference(case, n_iters, A, merit=False)
-    for key in ref:
-        assert np.array_equal(ref[key], mine[key]), key
+def test_without_the_merit_and_the_composition_the_loop_is_the_oracles_ilqr(case, n_iters, A):
+    """The one loop there is, with the oracle's own backward pass, one step size and no merit, on
+    the run's batch with its first record alone and no box: orc_ilqr bit for bit (the assertion of
+    test_line_search_host.py::test_one_step_size_is_the_oracles_ilqr_bit_for_bit on the sets of this
+    suite; `A` names the run the set is taken from)."""
+    from oracle import oracle as orc
+    cfg, host, _ = make_case(case, box=True)
+    if host["obs"].ndim == 3:
+        host = first_record_only(host)
+    want = orc.ilqr_batch(cfg, host["X"], host["U"], host["x_term"], host["lamb"], host["obs"],
+                          max_iter=n_iters, early_exit=n_iters is None)
+    got = reference(cfg, host, A=1, merit=False, oracle_backward=True, max_iter=n_iters,
+                    early_exit=n_iters is None)
+    for key in OUTPUTS:
+        assert np.array_equal(got[key], want[key], equal_nan=True), key
 
 
-@pytest.mark.parametrize("case,n_iters,A", bc.GPU_RUNS, ids=IDS)
+@pytest.mark.parametrize("case,n_iters,A", MERIT_RUNS, ids=IDS)
 def test_gpu_runs_meet_the_conditioning_rule(case, n_iters, A):
     """A problem is compared on the GPU only if its smallest deciding margin is >= 1e-7 (ten times
     the 1e-8 allowed on X and U).  A fixed-count run may leave out no problem, a termination run at
     most 20 %."""
     margin = _reference(case, n_iters, A)["margin"]
-    out = (margin < bc.MARGIN).mean()
-    print(f"{case}: smallest margin {margin.min():.3g}, {out:.1%} of the problems below {bc.MARGIN}")
-    assert out <= bc.MAX_LEFT_OUT[n_iters is None]
+    out = (margin < MARGIN).mean()
+    print(f"{case}: smallest margin {margin.min():.3g}, {out:.1%} of the problems below {MARGIN}")
+    assert out <= MAX_LEFT_OUT[n_iters is None]
 
 
 def test_the_unboxed_gpu_run_meets_the_conditioning_rule():
     """test_gpu_barrier_cost.py's run without a box (b4, three iterations) asks for 80 %."""
-    cfg, host = mo.ls_case("b4")
-    margin = bc.merit_reference(cfg, host, None, 1, max_iter=3, early_exit=False)["margin"]
+    cfg, host, _ = make_case("b4")
+    margin = reference(cfg, host, merit=True, max_iter=3, early_exit=False)["margin"]
     print(f"smallest margin {margin.min():.3g}")
-    assert (margin >= bc.MARGIN).mean() >= 0.8
+    assert (margin >= MARGIN).mean() >= 0.8
 
 
-@pytest.mark.parametrize("case,n_iters,A", bc.TERMINATION_RUNS,
-                         ids=[f"{c}-A{A}" for c, _, A in bc.TERMINATION_RUNS])
+@pytest.mark.parametrize("case,n_iters,A", MERIT_TERMINATION_RUNS,
+                         ids=[f"{c}-A{A}" for c, _, A in MERIT_TERMINATION_RUNS])
 def test_the_option_matters(case, n_iters, A):
     """The rule of the sibling suites: the option moves at least 15 % of the problems by more than
-    1e-3 relative (against box_reference, the soft accept test)."""
+    1e-3 relative (against the loop without the merit, the soft accept test)."""
     full, soft = _reference(case, None, A), _reference(case, None, A, merit=False)
     B = len(full["X"])
     d = (np.abs(full["X"] - soft["X"]).reshape(B, -1).max(axis=1) /
@@ -138,10 +147,10 @@ def test_closed_loop_laps_on_the_host():
     with the option on, with and without the speed-limit box: every lap finishes feasibly, in the
     golden file's steps and with its top speeds.  (The option does not harden the bound: the laps'
     top speeds stay where the barrier's stiffness q1 = q2 = 1 puts them.)"""
-    gold = bc.golden_laps()
-    for box, steps_key, top_key in ((None, "steps", "top"), (sb.speed_limit_box(), "steps_box", "top_box")):
-        steps, ego = sb.controlled_laps(bc.MeritCandidateSolver(box))
-        top = sb.top_speeds(ego)
+    gold = golden_laps("barrier_cost_laps")
+    for box, steps_key, top_key in ((None, "steps", "top"), (speed_limit_box(), "steps_box", "top_box")):
+        steps, ego = controlled_laps(ReferenceCandidateSolver(box, merit=True))
+        top = top_speeds(ego)
         print("box" if box is not None else "no box", "lap steps", steps, "top speeds", top)
         assert all(f.all() for f in ego.diagnostics["feasibility"])
         assert len(steps) == 4 and max(steps[1:]) < 120  # (a lap that runs out of time has 121 states)

@@ -4,11 +4,9 @@ batch-tiled.
 
 Off is off, disabled records are inert and a far box is no box, against the plain lane kernels bit
 for bit (the far box: as numbers).  K > 1 and a finite bound are compared with
-multi_obstacle_reference.mo_reference / state_box_reference.box_reference on the 67-problem sets
-test_obstacles_host.py / test_state_box_host.py show to be well conditioned, and on the two
-128-problem sets of lane_models_cases.py (test_lane_models_host.py).  Tolerances (fp64) are those of
-test_gpu_line_search._compare: X, U to TOL_SOLVE per problem, cost to 1e-8 relative, K to 1e-7 and k
-to 1e-7 with floor 1, on the problems that end with the reference's lamb; at least 97 % must.
+opt_in_reference.reference on the 67-problem sets test_obstacles_host.py / test_state_box_host.py
+show to be well conditioned, and on the two 128-problem sets of opt_in_cases.TILED
+(test_lane_models_host.py).  Tolerances and the 97 % rule: opt_in_gpu.compare.
 
 The N = 64 sets: no lane kernel has a recorded error at that horizon, so the bound is taken in the
 test from the plain lane kernel against the oracle's composition at one record (ten times its
@@ -18,12 +16,10 @@ import functools
 import numpy as np
 import pytest
 
-import lane_models_cases as lm
-import multi_obstacle_reference as mo
-import state_box_reference as sb
-from helpers import batch_rel_err, check_solve_outputs, dev_batch, to_host
-from test_gpu_line_search import OUTPUTS, _compare, _run, _same_bits
-from test_gpu_parity import TOL_SOLVE
+from helpers import TOL_SOLVE, batch_rel_err, check_solve_outputs, dev_batch, to_host
+from opt_in_cases import (BOX_RUNS, OBS_RUNS, SEED, TILED, TILED_RUNS, make_case, on_layout)
+from opt_in_gpu import OUTPUTS, compare, make_solver, run, same_bits
+from opt_in_reference import Box, first_record_only, reference
 
 pytestmark = pytest.mark.gpu
 
@@ -39,37 +35,19 @@ def torch_mod():
 
 
 @functools.lru_cache(maxsize=None)
-def _mo_reference(case, n_iters):
-    cfg, host = mo.make_case(case)
-    return mo.mo_reference(cfg, host, max_iter=n_iters, early_exit=n_iters is None)
-
-
-@functools.lru_cache(maxsize=None)
-def _box_reference(case, n_iters):
-    cfg, host, box = sb.make_case(case)
-    return sb.box_reference(cfg, host, box, max_iter=n_iters, early_exit=n_iters is None)
-
-
-@functools.lru_cache(maxsize=None)
-def _tiled_reference(name, n_iters, boxed):
-    cfg, host, box = lm.tiled_case(name)
-    return sb.box_reference(cfg, host, box if boxed else None, max_iter=n_iters,
-                            early_exit=n_iters is None)
+def _reference(case, n_iters, boxed, layout=0):
+    """reference() of a RECORDS entry, or (boxed) of a BOXES entry with its box."""
+    cfg, host, box = make_case(case, box=boxed, layout=layout)
+    return reference(cfg, host, box=box, max_iter=n_iters, early_exit=n_iters is None)
 
 
 def _lane(cfg, layout=1, models=True, obstacles=None, box=None, **options):
     """A solver of cfg on a lane layout: options, then "lane_models", then the models."""
-    from ilqr_iterative_tasks_amd import BatchedILQR
-    solver = BatchedILQR(lm.on_layout(cfg, layout))
-    for name, value in options.items():
-        solver.set_option(name, value)
     if models:
-        solver.set_option("lane_models", 1)
+        options["lane_models"] = 1
     if obstacles is not None:
-        solver.set_option("obstacles", obstacles)
-    if box is not None:
-        solver.set_state_box(box.lo, box.hi, box.q1, box.q2)
-    return solver
+        options["obstacles"] = obstacles
+    return make_solver(on_layout(cfg, layout), box, **options)
 
 
 def _records(host):
@@ -89,8 +67,7 @@ def _model_solver(cfg, host, box=None, layout=1, **options):
 
 def test_off_is_off(torch_mod):
     from ilqr_iterative_tasks_amd.solver import I2lqrError
-    cfg, host = mo.ls_case("b6")
-    _, _, box = sb.make_case("b6")
+    cfg, host, box = make_case("b6", box=True)
     B = host["X"].shape[0]
     plain = _lane(cfg, models=False)
     names = plain.iterate_kernel(B), plain.solve_kernel(B)
@@ -104,12 +81,12 @@ def test_off_is_off(torch_mod):
         plain.set_option("lane_models", value)
         with pytest.raises(I2lqrError, match="obstacles.*problem-major"):
             plain.set_option("obstacles", 2)
-    want = {n: _run(plain, host, n) for n in (6, None)}
+    want = {n: run(plain, host, n) for n in (6, None)}
     # on, with no model set: the plain kernels
     solver = _lane(cfg)
     assert (solver.iterate_kernel(B), solver.solve_kernel(B)) == names
     for n in (6, None):
-        _same_bits(torch_mod, _run(solver, host, n), want[n])
+        same_bits(torch_mod, run(solver, host, n), want[n])
     # a model on, then cleared: the names and the bits return
     solver.set_option("obstacles", 3)
     assert solver.iterate_kernel(B) == solver.solve_kernel(B) == OBS_NAME
@@ -120,18 +97,14 @@ def test_off_is_off(torch_mod):
     solver.set_state_box()
     assert (solver.iterate_kernel(B), solver.solve_kernel(B)) == names
     for n in (6, None):
-        _same_bits(torch_mod, _run(solver, host, n), want[n])
+        same_bits(torch_mod, run(solver, host, n), want[n])
     solver.set_option("lane_models", 0)
     assert (solver.iterate_kernel(B), solver.solve_kernel(B)) == names
 
 
 def _plain_batch(case, layout):
-    """(cfg, host with obs[B, 6]): the 67 problems of ls_case, or the 128 of the tiled sets."""
-    if layout == 1:
-        return mo.ls_case(case)
-    from ilqr_iterative_tasks_amd import workloads
-    cfg, host, _ = lm.tiled_case({"b4": "b4_T128_K2", "b6": "b6_T128_K3"}[case])
-    return cfg, workloads.make_batch(cfg, 128)
+    """(cfg, host with obs[B, 6]): the 67 problems of the set, or the 128 under the tiled sets."""
+    return make_case(case)[:2] if layout == 1 else make_case(case + "_T128", layout=2)[:2]
 
 
 @pytest.mark.parametrize("layout", [1, 2])
@@ -152,20 +125,20 @@ def test_disabled_records_are_inert(torch_mod, case, layout):
     first[:, 0] = single["obs"]
     plain = _lane(cfg, layout, models=False)
     for n in (6, None):
-        want = _run(plain, single, n)
+        want = run(plain, single, n)
         for recs in (middle, first):
             batch = dict(host, obs=recs)
-            _same_bits(torch_mod, _run(_model_solver(cfg, batch, layout=layout), batch, n), want)
+            same_bits(torch_mod, run(_model_solver(cfg, batch, layout=layout), batch, n), want)
 
 
 @pytest.mark.parametrize("layout", [1, 2])
 def test_null_obs_is_no_obstacle(torch_mod, layout):
     cfg, host = _plain_batch("b6", layout)
     host = dict(host, obs=None)
-    want = _run(_lane(cfg, layout, models=False), host, 5)
+    want = run(_lane(cfg, layout, models=False), host, 5)
     solver = _lane(cfg, layout, obstacles=2)
     assert solver.iterate_kernel(host["X"].shape[0]) == OBS_NAME
-    _same_bits(torch_mod, _run(solver, host, 5), want)
+    same_bits(torch_mod, run(solver, host, 5), want)
 
 
 @pytest.mark.parametrize("case", ["b4", "b6"])
@@ -174,31 +147,33 @@ def test_a_far_box_is_no_box(torch_mod, case):
     plain lane kernel's, with two records the K = 2 model kernel's — as numbers (adding an exact
     zero may turn -0.0 into +0.0).  A term added to the wrong element would show."""
     from ilqr_iterative_tasks_amd import workloads
-    cfg, host = mo.ls_case(case)
-    far = sb.Box(cfg.n, {i: (-1e6, 1e6) for i in range(cfg.n)})
+    cfg, host, _ = make_case(case)
+    far = Box(cfg.n, {i: (-1e6, 1e6) for i in range(cfg.n)})
     two = dict(host, obs=workloads.obstacles_on_path(host, 2, 7))
     for batch, base in ((host, _lane(cfg, models=False)), (two, _model_solver(cfg, two))):
         boxed = _model_solver(cfg, batch, far)
         for n in (6, None):
-            want, got = _run(base, batch, n), _run(boxed, batch, n)
+            want, got = run(base, batch, n), run(boxed, batch, n)
             for key in OUTPUTS:
                 assert torch_mod.equal(got[key], want[key]), (key, n, _records(batch))
 
 
 def _check_records(case, n_iters):
-    cfg, host = mo.make_case(case)
+    assert (case, n_iters) in OBS_RUNS
+    cfg, host, _ = make_case(case)
     solver = _model_solver(cfg, host)
-    buf = _run(solver, host, n_iters)
-    _compare(solver, buf, _mo_reference(case, n_iters), n_iters)
+    buf = run(solver, host, n_iters)
+    compare(solver, buf, _reference(case, n_iters, False), n_iters)
     return solver, cfg, host, buf
 
 
 def _check_box(case, n_iters):
-    cfg, host, box = sb.make_case(case)
+    assert (case, n_iters, 1) in BOX_RUNS
+    cfg, host, box = make_case(case, box=True)
     solver = _model_solver(cfg, host, box)
     assert solver.state_box is not None
-    buf = _run(solver, host, n_iters)
-    _compare(solver, buf, _box_reference(case, n_iters), n_iters)
+    buf = run(solver, host, n_iters)
+    compare(solver, buf, _reference(case, n_iters, True), n_iters)
     return solver, cfg, host, buf
 
 
@@ -234,20 +209,21 @@ def test_box_solve_to_termination_matches_the_reference(torch_mod, case):
     check_solve_outputs(solver, cfg, host, buf)
 
 
-@pytest.mark.parametrize("name", sorted(lm.TILED))
+@pytest.mark.parametrize("name", TILED)
 def test_tiled_sets_match_the_reference(torch_mod, name):
     """The batch-tiled layout, two wavefronts: the records for 6 iterations, records and box solved."""
-    cfg, host, box = lm.tiled_case(name)
+    cfg, host, box = make_case(name, box=True, layout=2)
+    assert [r[1:] for r in TILED_RUNS if r[0] == name] == [(6, False), (None, True)]
     solver = _model_solver(cfg, host, layout=2)
-    _compare(solver, _run(solver, host, 6), _tiled_reference(name, 6, False), 6)
+    compare(solver, run(solver, host, 6), _reference(name, 6, False, layout=2), 6)
     solver = _model_solver(cfg, host, box, layout=2)
-    buf = _run(solver, host, None)
-    _compare(solver, buf, _tiled_reference(name, None, True), None)
+    buf = run(solver, host, None)
+    compare(solver, buf, _reference(name, None, True, layout=2), None)
     check_solve_outputs(solver, cfg, host, buf)
 
 
 def _errors(solver, buf, ref):
-    """(X, U) batch_rel_err on the problems that took the reference's branches, as _compare picks
+    """(X, U) batch_rel_err on the problems that took the reference's branches, as compare picks
     them: all iterations run, at least 97 % with the reference's lamb, their status words equal."""
     same = buf["lamb"].cpu().numpy() == ref["lamb"]
     assert (buf["iters"].cpu().numpy() == 5).all()
@@ -262,16 +238,12 @@ def test_long_horizon_error_is_the_plain_lane_kernels(torch_mod, case, boxed):
     """N = 64: the model kernel's error on X and U against its reference is at most ten times the
     plain lane kernel's against the oracle's composition at one record on the same batch (the
     extra records and the box add terms of the same size and kind), or TOL_SOLVE if that is larger."""
-    if boxed:
-        cfg, host, box = sb.make_case(case)
-        one, ref = host, _box_reference(case, 5)
-    else:
-        cfg, host = mo.make_case(case)
-        box, one, ref = None, mo.first_record_only(host), _mo_reference(case, 5)
+    cfg, host, box = make_case(case, box=boxed)
+    one, ref = host if boxed else first_record_only(host), _reference(case, 5, boxed)
     plain = _lane(cfg, models=False)
-    base = _errors(plain, _run(plain, one, 5), mo.mo_reference(cfg, one, max_iter=5, early_exit=False))
+    base = _errors(plain, run(plain, one, 5), reference(cfg, one, max_iter=5, early_exit=False))
     solver = _model_solver(cfg, host, box)
-    got = _errors(solver, _run(solver, host, 5), ref)
+    got = _errors(solver, run(solver, host, 5), ref)
     print(f"{case}: plain lane kernel X {base[0]:.3e} U {base[1]:.3e}; "
           f"model kernel X {got[0]:.3e} U {got[1]:.3e}")
     for mine, plain_err in zip(got, base):
@@ -284,37 +256,37 @@ def test_scheduling_options_keep_the_bits(torch_mod, K):
     automatic choice, with a box and K records: the records' LDS overlapping the gain steps would
     show; K = 8 leaves the fewest gain steps."""
     from ilqr_iterative_tasks_amd import workloads
-    cfg, host, box = sb.make_case("b6")
-    host = mo.make_case("b6_K3")[1] if K == 3 else dict(host, obs=workloads.obstacles_on_path(host, 8, mo.SEED))
+    cfg, host, box = make_case("b6", box=True)
+    host = make_case("b6_K3")[1] if K == 3 else dict(host, obs=workloads.obstacles_on_path(host, 8, SEED))
     variants = [dict(defer_states=d, reroll_nominal=r) for d in (0, 1) for r in (0, 1)]
     variants += [dict(merge_inputs=1), dict(lds_gain_steps=0), dict(stagger=2)]
     for n in (6, None):
         base = _model_solver(cfg, host, box)
-        want = _run(base, host, n)
+        want = run(base, host, n)
         for options in variants + [dict(helper_wavefront=1, checkpoint_states=1, state_buffers=1)]:
-            _same_bits(torch_mod, _run(_model_solver(cfg, host, box, **options), host, n), want)
+            same_bits(torch_mod, run(_model_solver(cfg, host, box, **options), host, n), want)
 
 
 @pytest.mark.parametrize("layout", [1, 2])
 def test_fp32_outputs_are_consistent(torch_mod, layout):
     if layout == 1:
-        cfg, host = mo.make_case("b6_K2", "f32")
-        _, plain_host, box = sb.make_case("b6", "f32")
+        cfg, host, _ = make_case("b6_K2", dtype="f32")
+        _, plain_host, box = make_case("b6", box=True, dtype="f32")
     else:
-        cfg, host, box = lm.tiled_case("b6_T128_K3", "f32")
-        plain_host = mo.first_record_only(host)
+        cfg, host, box = make_case("b6_T128_K3", box=True, dtype="f32", layout=2)
+        plain_host = first_record_only(host)
     for batch, bx in ((host, None), (plain_host, box)):
         solver = _model_solver(cfg, batch, bx, layout=layout)
-        buf = _run(solver, batch, 6)
+        buf = run(solver, batch, 6)
         check_solve_outputs(solver, cfg, batch, buf, early_exit=False, n_iters=6)
-        buf = _run(solver, batch, None)
+        buf = run(solver, batch, None)
         check_solve_outputs(solver, cfg, batch, buf)
 
 
 def test_names_and_refusals(torch_mod):
     from ilqr_iterative_tasks_amd import BatchedILQR, default_config
     from ilqr_iterative_tasks_amd.solver import I2lqrError
-    cfg, host, box = sb.make_case("b6_K2")
+    cfg, host, box = make_case("b6_K2", box=True)
     B = host["X"].shape[0]
     solver = _lane(cfg, obstacles=2)
     assert solver.iterate_kernel(B) == solver.solve_kernel(B) == OBS_NAME
@@ -367,10 +339,10 @@ def test_solve_stays_a_single_launch(torch_mod):
     from ilqr_iterative_tasks_amd import default_config, workloads
     cfg = default_config("bicycle6", 20, dt=0.25)
     host = workloads.make_batch(cfg, 4160)
-    host = dict(host, obs=workloads.obstacles_on_path(host, 2, mo.SEED))
+    host = dict(host, obs=workloads.obstacles_on_path(host, 2, SEED))
     solver = _model_solver(cfg, host)
-    want = _run(solver, host, None)
+    want = run(solver, host, None)
     check_solve_outputs(solver, cfg, host, want)
     solver.set_compaction(64)
     assert solver.solve_kernel(4160) == OBS_NAME
-    _same_bits(torch_mod, _run(solver, host, None), want)
+    same_bits(torch_mod, run(solver, host, None), want)

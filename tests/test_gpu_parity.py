@@ -10,13 +10,12 @@ reference's own output by 3.4e-9 (chaotic amplification through up to 150 iterat
 import numpy as np
 import pytest
 
-from helpers import (batch_rel_err, check_solve_outputs, dev_batch, problems_from_calls, rel_err,
-                     to_dev, to_host)
+from helpers import (TOL_SOLVE, batch_rel_err, check_solve_outputs, dev_batch, problems_from_calls,
+                     rel_err, to_dev, to_host)
 
 pytestmark = pytest.mark.gpu
 
-TOL_FUNC = 1e-10   # one backward / forward pass, fp64
-TOL_SOLVE = 1e-8   # whole ilqr(), fp64 (north_star tolerance)
+TOL_FUNC = 1e-10   # one backward / forward pass, fp64 (TOL_SOLVE, the whole ilqr(): helpers.py)
 
 
 @pytest.fixture(scope="module")

@@ -10,9 +10,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import lane_models_cases as lm
-import multi_obstacle_reference as mo
-import state_box_reference as sb
+from opt_in_cases import RECORDS, TILED, TILED_RUNS, make_case
+from opt_in_reference import first_record_only, reference
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "ilqr_iterative_tasks_amd" / "csrc"
@@ -190,17 +189,12 @@ def test_header_documents_the_option_and_the_layouts():
     assert "i2lqr_lane_model_f64" in units and "i2lqr_lane_model_f32" in units
 
 
-# (set, fixed iterations or None for a solve, with the box): what test_gpu_lane_models.py compares
-# with mo_reference / box_reference on the batch-tiled sets
-TILED_RUNS = [(name, n, boxed) for name in sorted(lm.TILED) for n, boxed in ((6, False), (None, True))]
-
-
 @functools.lru_cache(maxsize=None)
 def _reference(name, n_iters, boxed, scale=1.0):
-    cfg, host, box = lm.tiled_case(name)
+    cfg, host, box = make_case(name, box=True, layout=2)
     host = dict(host, X=host["X"] * scale)  # (only X[:, :, 0] = x0 is non-zero)
-    return sb.box_reference(cfg, host, box if boxed else None, max_iter=n_iters,
-                            early_exit=n_iters is None)
+    return reference(cfg, host, box=box if boxed else None, max_iter=n_iters,
+                     early_exit=n_iters is None)
 
 
 @pytest.mark.parametrize("name,n_iters,boxed", TILED_RUNS,
@@ -216,15 +210,15 @@ def test_tiled_sets_are_well_conditioned(name, n_iters, boxed):
         assert np.array_equal(per["iters"], ref["iters"]), scale
 
 
-@pytest.mark.parametrize("name", sorted(lm.TILED))
+@pytest.mark.parametrize("name", TILED)
 def test_tiled_sets_extra_records_and_box_matter(name):
     """The sets exercise what they are for: the records beyond the first and the box each move the
     trajectories of at least a tenth of the problems by more than 1e-6 relative."""
-    cfg, host, box = lm.tiled_case(name)
-    assert host["X"].shape[0] == 128 and host["obs"].shape[1:] == (lm.TILED[name][3], 6)
+    cfg, host, box = make_case(name, box=True, layout=2)
+    assert host["X"].shape[0] == 128 and host["obs"].shape[1:] == (RECORDS[name][1], 6)
     full = _reference(name, 6, False)
-    one = mo.mo_reference(cfg, mo.first_record_only(host), max_iter=6, early_exit=False)
-    boxed = sb.box_reference(cfg, host, box, max_iter=6, early_exit=False)
+    one = reference(cfg, first_record_only(host), max_iter=6, early_exit=False)
+    boxed = reference(cfg, host, box=box, max_iter=6, early_exit=False)
     for other in (one, boxed):
         d = (np.abs(full["X"] - other["X"]).reshape(128, -1).max(axis=1) /
              np.abs(full["X"]).reshape(128, -1).max(axis=1))

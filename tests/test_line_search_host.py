@@ -1,39 +1,42 @@
 """CPU suite of the "line_search" option: the host reference the GPU tests compare with
-(ls_reference.py) is the oracle's ilqr() at one step size, every problem set the GPU tests use is
-well conditioned (its step choices and lamb survive a perturbation of x0 far above the kernels'
-round-off), the sets take short steps, and the header documents the option."""
+(opt_in_reference.reference with the oracle's backward pass) is the oracle's ilqr() at one step
+size, every problem set the GPU tests use is well conditioned (its step choices and lamb survive a
+perturbation of x0 far above the kernels' round-off), the sets take short steps, and the header
+documents the option."""
 import functools
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from ls_reference import (GPU_RUNS, candidate_case, ls_reference, make_case, short_step_share)
+from opt_in_cases import LS_RUNS, candidate_case, make_case
+from opt_in_reference import OUTPUTS, reference, short_step_share
 
 ROOT = Path(__file__).resolve().parent.parent
 
 
 @functools.lru_cache(maxsize=None)
 def _reference(case, A, n_iters, scale=1.0):
-    cfg, host = make_case(case) if case != "candidates" else (candidate_case()[0], candidate_case()[4])
+    cfg, host = make_case(case)[:2] if case != "candidates" else candidate_case()[::4]
     host = dict(host, X=host["X"] * scale)  # (only X[:, :, 0] = x0 is non-zero)
-    return ls_reference(cfg, host, A, max_iter=n_iters, early_exit=n_iters is None)
+    return reference(cfg, host, A, oracle_backward=True, max_iter=n_iters,
+                     early_exit=n_iters is None)
 
 
 @pytest.mark.parametrize("n_iters", [None, 6])
 @pytest.mark.parametrize("case", ["b4_weights", "b4", "b6", "quad12"])
 def test_one_step_size_is_the_oracles_ilqr_bit_for_bit(case, n_iters):
     from oracle import oracle as orc
-    cfg, host = make_case(case)
+    cfg, host, _ = make_case(case)
     want = orc.ilqr_batch(cfg, host["X"], host["U"], host["x_term"], host["lamb"], host["obs"],
                           max_iter=n_iters, early_exit=n_iters is None)
     got = _reference(case, 1, n_iters)
-    for key in ("X", "U", "lamb", "cost", "iters", "status", "K", "k"):
+    for key in OUTPUTS:
         assert np.array_equal(got[key], want[key], equal_nan=True), key
     assert (got["jstar"] <= 0).all()
 
 
-RUNS = list(GPU_RUNS) + [("candidates", 4, None, 0.0)]
+RUNS = list(LS_RUNS) + [("candidates", 4, None, 0.0)]
 
 
 @pytest.mark.parametrize("case,A,n_iters,share", RUNS,

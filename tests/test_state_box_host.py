@@ -1,6 +1,6 @@
 """CPU suite of the state box (i2lqr_set_state_box, include/i2lqr.h): the host reference the GPU
-tests compare with (state_box_reference.py) is multi_obstacle_reference's without a bound, its
-barrier terms are the derivatives they claim to be, every problem set the GPU tests use is well
+tests compare with (opt_in_reference.py) is the reference without a box where no bound is finite,
+its barrier terms are the derivatives they claim to be, every problem set the GPU tests use is well
 conditioned and its box bends the trajectories, the speed-limit closed loop finishes its laps slower
 than the free one, and StateBox / state_box_from_params do what they say."""
 import functools
@@ -9,43 +9,47 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import multi_obstacle_reference as mo
-import state_box_reference as sb
 from helpers import OracleCandidateSolver
+from opt_in_cases import BOX_RUNS, make_case, run_id
+from opt_in_reference import (LAP_STEPS_LIMIT, LAP_STEPS_ONE, OUTPUTS, SPEED_LIMIT, Box,
+                              ReferenceCandidateSolver, barrier_terms, composed_backward,
+                              controlled_laps, golden_laps, reference, speed_limit_box, top_speeds)
 
 ROOT = Path(__file__).resolve().parent.parent
-IDS = [f"{c}-{'solve' if i is None else i}-A{A}" for c, i, A in sb.GPU_RUNS]
+IDS = [run_id(*run) for run in BOX_RUNS]
 
 
 @functools.lru_cache(maxsize=None)
 def _reference(case, n_iters, A=1, boxed=True, scale=1.0):
-    cfg, host, box = sb.make_case(case)
+    cfg, host, box = make_case(case, box=True)
     host = dict(host, X=host["X"] * scale)  # (only X[:, :, 0] = x0 is non-zero)
-    return sb.box_reference(cfg, host, box if boxed else None, A, max_iter=n_iters,
-                            early_exit=n_iters is None)
+    return reference(cfg, host, A, box=box if boxed else None, max_iter=n_iters,
+                     early_exit=n_iters is None)
 
 
 @pytest.mark.parametrize("case", ["b4", "b6_K2", "quad12"])
 def test_without_a_finite_bound_the_pass_is_the_obstacle_references(case):
     from oracle import oracle as orc
-    cfg, host, _ = sb.make_case(case)
+    cfg, host, _ = make_case(case, box=True)
     X, U, _ = orc.rollout_batch(cfg, host["X"], host["U"], host["x_term"])
-    want = mo.composed_backward(cfg, X, U, host["x_term"], host["lamb"], host["obs"])
-    for box in (None, sb.Box(cfg.n, {}), sb.Box(cfg.n, {1: (None, None)})):
-        got = sb.composed_backward(cfg, X, U, host["x_term"], host["lamb"], host["obs"], box)
+    want = composed_backward(cfg, X, U, host["x_term"], host["lamb"], host["obs"])
+    inactive = (Box(cfg.n, {}), Box(cfg.n, {1: (None, None)}))
+    for box in (None,) + inactive:
+        got = composed_backward(cfg, X, U, host["x_term"], host["lamb"], host["obs"], box)
         assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
-    # ... and the whole loop mo_reference's
-    ref, mine = mo.mo_reference(cfg, host, max_iter=3, early_exit=False), \
-        sb.box_reference(cfg, host, None, max_iter=3, early_exit=False)
-    for key in ref:
-        assert np.array_equal(ref[key], mine[key]), key
+    # ... and the whole loop the one without a box
+    ref = reference(cfg, host, box=None, max_iter=3, early_exit=False)
+    for box in inactive:
+        mine = reference(cfg, host, box=box, max_iter=3, early_exit=False)
+        for key in OUTPUTS:
+            assert np.array_equal(ref[key], mine[key]), key
 
 
 def test_bounds_far_away_add_exact_zeros():
     """What test_gpu_state_box.py's "the rest of the kernel is untouched" relies on."""
-    cfg, host, _ = sb.make_case("b6")
-    box = sb.Box(cfg.n, {i: (-1e6, 1e6) for i in range(cfg.n)})
-    d1, d2 = sb.barrier_terms(box, np.random.default_rng(0).normal(0, 50, (3, cfg.n, 21)))
+    cfg, host, _ = make_case("b6")
+    box = Box(cfg.n, {i: (-1e6, 1e6) for i in range(cfg.n)})
+    d1, d2 = barrier_terms(box, np.random.default_rng(0).normal(0, 50, (3, cfg.n, 21)))
     assert not d1.any() and not d2.any()
 
 
@@ -56,7 +60,7 @@ def test_barrier_terms_are_the_barriers_derivatives(q2):
     size of the term without cancellation, q2 (q1 e_hi + q1 e_lo) for d1 and q2 times that for d2
     (truncation h^2 q2^2 / 6 <= 7e-9 and rounding eps / (h q2) <= 3e-11 of it at q2 <= 20)."""
     q1, h = 0.7, 1e-5
-    box = sb.Box(3, {0: (-0.3, 0.4), 1: (None, 0.1), 2: (-0.2, None)}, q1, q2)
+    box = Box(3, {0: (-0.3, 0.4), 1: (None, 0.1), 2: (-0.2, None)}, q1, q2)
     x = np.random.default_rng(1).uniform(-0.5, 0.5, (5, 3, 7))
 
     def barrier(x):
@@ -68,17 +72,17 @@ def test_barrier_terms_are_the_barriers_derivatives(q2):
                 out[:, i] += q1 * np.exp(q2 * (box.lo[i] - x[:, i]))
         return out
 
-    d1, d2 = sb.barrier_terms(box, x)
+    d1, d2 = barrier_terms(box, x)
     size = q2 * barrier(x)
     assert (size > 0).all()
     n1 = (barrier(x + h) - barrier(x - h)) / (2 * h)
-    n2 = (sb.barrier_terms(box, x + h)[0] - sb.barrier_terms(box, x - h)[0]) / (2 * h)
+    n2 = (barrier_terms(box, x + h)[0] - barrier_terms(box, x - h)[0]) / (2 * h)
     assert (np.abs(d1 - n1) <= 1e-6 * size).all()
     assert (np.abs(d2 - n2) <= 1e-6 * q2 * size).all()
     assert (d2 > 0).all() and (d1[:, 1] > 0).all() and (d1[:, 2] < 0).all()
 
 
-@pytest.mark.parametrize("case,n_iters,A", sb.GPU_RUNS, ids=IDS)
+@pytest.mark.parametrize("case,n_iters,A", BOX_RUNS, ids=IDS)
 def test_gpu_cases_are_well_conditioned(case, n_iters, A):
     """A kernel that differs from the reference by round-off must meet the same accept / reject
     decisions: they do not move when x0 is scaled by 1 + 1e-13 or 1 - 1e-12."""
@@ -90,7 +94,7 @@ def test_gpu_cases_are_well_conditioned(case, n_iters, A):
         assert np.array_equal(per["status"], ref["status"]), scale
 
 
-@pytest.mark.parametrize("case,n_iters,A", sb.GPU_RUNS, ids=IDS)
+@pytest.mark.parametrize("case,n_iters,A", BOX_RUNS, ids=IDS)
 def test_the_box_matters(case, n_iters, A):
     """The rule of test_obstacles_host.py::test_the_extra_records_matter: the box moves at least
     15 % of the problems by more than 1e-3 relative."""
@@ -106,19 +110,19 @@ def test_speed_limit_laps_on_the_host():
     """Config 1 (N = 6, 2 x 8 candidates, chained lamb, the static obstacle) for three controlled
     laps with v in [0, 8]: every lap finishes, in the golden file's steps, which are not the free
     loop's, and the controlled laps' top speed is lower than the free loop's."""
-    steps, ego = sb.controlled_laps(sb.BoxCandidateSolver(sb.speed_limit_box()))
-    free, ego_free = sb.controlled_laps(OracleCandidateSolver())
-    gold = sb.golden_laps()
-    assert steps == sb.LAP_STEPS == list(gold["steps"])
-    assert free == sb.LAP_STEPS_ONE and steps != free
+    steps, ego = controlled_laps(ReferenceCandidateSolver(speed_limit_box()))
+    free, ego_free = controlled_laps(OracleCandidateSolver())
+    gold = golden_laps("state_box_laps")
+    assert steps == LAP_STEPS_LIMIT == list(gold["steps"])
+    assert free == LAP_STEPS_ONE and steps != free
     np.testing.assert_allclose(ego.data["input"][0], gold["inputs"], rtol=0, atol=1e-6)
     assert all(f.all() for f in ego.diagnostics["feasibility"])
     assert max(steps[1:]) < 120  # (a lap that runs out of time has 121 states)
-    top, top_free = sb.top_speeds(ego), sb.top_speeds(ego_free)
+    top, top_free = top_speeds(ego), top_speeds(ego_free)
     print("top speeds with the limit", top, "without", top_free)
     np.testing.assert_allclose(top, gold["top"], rtol=0, atol=1e-6)
     assert max(top) < max(top_free)
-    assert max(top) < sb.SPEED_LIMIT[1] + 1.5  # soft, as the input barrier is: 8.96 at most
+    assert max(top) < SPEED_LIMIT[1] + 1.5  # soft, as the input barrier is: 8.96 at most
 
 
 def test_state_box_and_state_box_from_params():
@@ -149,8 +153,8 @@ def test_a_boxed_solver_refuses_the_device_rounds_and_keys_its_handles():
     assert HipCandidateSolver(state_box=StateBox([-np.inf] * 4, [np.inf] * 4)).state_box is None
     assert HipCandidateSolver().state_box is None
     with pytest.raises(ValueError, match="state box"):
-        sb.controlled_laps(HipCandidateSolver(state_box=limit), laps=1, lamb_mode="independent",
-                           device_rounds=True)
+        controlled_laps(HipCandidateSolver(state_box=limit), laps=1, lamb_mode="independent",
+                        device_rounds=True)
     with pytest.raises(ValueError, match="state box"):
         HipCandidateSolver(state_box=limit).candidate_round(None, None, None, None, 1.0)
     with pytest.raises(ValueError, match="state box"):

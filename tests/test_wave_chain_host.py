@@ -1,5 +1,5 @@
 """CPU suite of the "wave_chain" option (include/i2lqr.h): the chain reference the GPU tests compare
-with (chain_reference.py) is state_box_reference.box_reference composed step by step; every problem
+with (opt_in_reference.chain_reference) is reference() composed step by step; every problem
 set the GPU tests use depends on the carried lamb and is well conditioned under it; the header
 documents the option and HipCandidateSolver passes it on."""
 import functools
@@ -8,35 +8,35 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import chain_reference as cr
-import state_box_reference as sb
+from opt_in_cases import CHAIN_SHAPES, make_chain
+from opt_in_reference import CHAIN_KEYS, chain_reference, reference, step_batch, step_index
 
 ROOT = Path(__file__).resolve().parent.parent
 CPU_CHAINS = 16  # of a larger shape the first 16 chains: what holds for them holds for the set
-CHAINED = [name for name, shape in cr.SHAPES.items() if shape[3] > 1]
+CHAINED = [name for name, shape in CHAIN_SHAPES.items() if shape[3] > 1]
 
 
 @functools.lru_cache(maxsize=None)
 def _shape(name):
-    cfg, host, box, A, chains, chain_len = cr.make_shape(name)
+    cfg, host, box, A, chains, chain_len = make_chain(name)
     if chains > CPU_CHAINS:
         chains = CPU_CHAINS
-        host = cr.step_batch(host, np.arange(chains * chain_len))
+        host = step_batch(host, np.arange(chains * chain_len))
     return cfg, host, box, A, chains, chain_len
 
 
 @functools.lru_cache(maxsize=None)
 def _chain(name):
-    return cr.chain_reference(*_shape(name))
+    return chain_reference(*_shape(name))
 
 
 @pytest.mark.parametrize("name", ["b6_1x1", "b4_5x1"])
 def test_a_chain_of_one_is_the_box_reference(name):
     cfg, host, box, A, chains, chain_len = _shape(name)
     assert chain_len == 1
-    want = sb.box_reference(cfg, host, box, A, early_exit=True)
+    want = reference(cfg, host, A, box=box)
     got = _chain(name)
-    for key in cr.OUT_KEYS:
+    for key in CHAIN_KEYS:
         assert np.array_equal(got[key], want[key]), key
 
 
@@ -45,11 +45,11 @@ def test_the_steps_are_box_references_with_the_previous_lamb():
     got = _chain("b4_3x4")
     lamb = None
     for c in range(chain_len):
-        idx = cr.step_index(chains, chain_len, c)
+        idx = step_index(chains, chain_len, c)
         if c == 0:
-            assert np.array_equal(cr.step_batch(host, idx)["lamb"], host["lamb"][idx])
-        want = sb.box_reference(cfg, cr.step_batch(host, idx, lamb), box, A, early_exit=True)
-        for key in cr.OUT_KEYS:
+            assert np.array_equal(step_batch(host, idx)["lamb"], host["lamb"][idx])
+        want = reference(cfg, step_batch(host, idx, lamb), A, box=box)
+        for key in CHAIN_KEYS:
             assert np.array_equal(got[key][idx], want[key]), (key, c)
         lamb = want["lamb"]
 
@@ -59,15 +59,15 @@ def test_the_carry_matters(name):
     """At least one problem of chain step 1 ends with another iteration count or lamb than the
     same problem started from its own lamb: a kernel that forgets the carry cannot pass."""
     cfg, host, box, A, chains, chain_len = _shape(name)
-    idx = cr.step_index(chains, chain_len, 1)
-    alone = sb.box_reference(cfg, cr.step_batch(host, idx), box, A, early_exit=True)
+    idx = step_index(chains, chain_len, 1)
+    alone = reference(cfg, step_batch(host, idx), A, box=box)
     got = _chain(name)
     differs = (alone["iters"] != got["iters"][idx]) | (alone["lamb"] != got["lamb"][idx])
     print(f"{name}: the carry changes {differs.sum()} of {len(idx)} problems of step 1")
     assert differs.any()
 
 
-@pytest.mark.parametrize("name", list(cr.SHAPES))
+@pytest.mark.parametrize("name", list(CHAIN_SHAPES))
 def test_gpu_shapes_are_well_conditioned_under_the_carried_lamb(name):
     """test_state_box_host.py's measure on every chain step, started from the lamb the reference
     carried into it: with x0 scaled by 1 + 1e-13 or 1 - 1e-12 at least 97 % of the problems keep the
@@ -78,9 +78,9 @@ def test_gpu_shapes_are_well_conditioned_under_the_carried_lamb(name):
         moved = dict(host, X=host["X"] * scale)  # (only X[:, :, 0] = x0 is non-zero)
         same = np.zeros(chains * chain_len, bool)
         for c in range(chain_len):
-            idx = cr.step_index(chains, chain_len, c)
-            lamb = None if c == 0 else ref["lamb"][cr.step_index(chains, chain_len, c - 1)]
-            per = sb.box_reference(cfg, cr.step_batch(moved, idx, lamb), box, A, early_exit=True)
+            idx = step_index(chains, chain_len, c)
+            lamb = None if c == 0 else ref["lamb"][step_index(chains, chain_len, c - 1)]
+            per = reference(cfg, step_batch(moved, idx, lamb), A, box=box)
             same[idx] = ((per["lamb"] == ref["lamb"][idx]) & (per["iters"] == ref["iters"][idx]) &
                          (per["status"] == ref["status"][idx]))
         print(f"{name} x {scale}: {same.mean():.3f} of {len(same)} problems keep their branch")

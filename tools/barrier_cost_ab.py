@@ -9,7 +9,7 @@ on handles of the same shape - time per 10 fixed iterations (device events, medi
 repetitions, the variants alternating inside every repetition, every launch on its own copy of the
 batch) and the share of the 10 iterations that were accepted.  --variant-lib adds k_iterate_merit of
 another build of the library (make variant ...) as a third variant.
-Then, for the termination runs of tests/barrier_cost_reference.py (and b4_weights), the share of
+Then, for opt_in_cases.MERIT_TERMINATION_RUNS of tests/ (and b4_weights), the share of
 LAMB_OVERFLOW exits and the mean final J with the option off and on.
 Writes JSON (default profiles/barrier_cost_ab.json).  Not part of bench.py, not a test.
 """
@@ -77,9 +77,10 @@ def measure(cfg, B, steps, comp, bound, q2, reps, variant_lib):
 def termination(case, A):
     """LAMB_OVERFLOW exits and the mean final J of a problem set solved to termination, the option
     off (J computed on the host from the returned trajectory) and on."""
-    import barrier_cost_reference as bc
     from helpers import dev_batch, to_host
-    cfg, host, box = bc.make_case(case)
+    from opt_in_cases import make_case
+    from opt_in_reference import penalty
+    cfg, host, box = make_case(case, box=True)
     out = {}
     for merit in (False, True):
         solver = BatchedILQR(cfg)
@@ -92,7 +93,7 @@ def termination(case, A):
         buf = solver.solve(dev_batch(solver, host))
         X, U = to_host(solver, buf["X"]), to_host(solver, buf["U"])
         cost = buf["cost"].cpu().numpy()
-        J = cost if merit else cost + bc.penalty(cfg, X, U, host["obs"], box)
+        J = cost if merit else cost + penalty(cfg, X, U, host["obs"], box)
         out["merit" if merit else "soft"] = dict(
             lamb_overflow=int((buf["status"].cpu().numpy() == 3).sum()), mean_final_J=float(J.mean()),
             mean_iters=float(buf["iters"].cpu().numpy().mean()))
