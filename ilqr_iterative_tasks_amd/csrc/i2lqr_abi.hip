@@ -619,6 +619,9 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
       return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_models\" is built for the batch-minor / batch-tiled "
                   "layouts (a problem-major handle runs the models on the one-problem-per-wavefront "
                   "kernels without it)");
+    if (v != 1 && h->lane_barrier_cost)
+      return fail(I2LQR_ERR_INVALID, "\"lane_models\" cannot be switched off while "
+                  "\"lane_barrier_cost\" is on: set \"lane_barrier_cost\" to 0 first");
     if (v != 1 && h->lane_models && (h->model.obs > 1 || h->model.box.on()))
       return fail(I2LQR_ERR_INVALID, "\"lane_models\" cannot be switched off while %s on: %s first",
                   h->model.box.on() ? "a state box is" : "\"obstacles\" is",
@@ -629,8 +632,27 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   else if (!strcmp(name, "barrier_cost")) {
     if (v != -1 && v != 0 && v != 1)
       return fail(I2LQR_ERR_INVALID, "\"barrier_cost\" is 1 (on), or -1 / 0 (off)");
-    if (v == 1 && !problem_major(h)) return refuse_layout(wave_phrase(WAVE_MERIT));
+    if (v == 1 && !problem_major(h))
+      return fail(I2LQR_ERR_UNSUPPORTED, "%s is built for the problem-major layout (the "
+                  "one-problem-per-wavefront kernel); a batch-minor / batch-tiled handle of the "
+                  "bicycles has \"lane_barrier_cost\" (with \"lane_models\" 1)",
+                  wave_phrase(WAVE_MERIT));
     h->model.barrier_cost = v == 1;
+  }
+  else if (!strcmp(name, "lane_barrier_cost")) {
+    if (v != -1 && v != 0 && v != 1)
+      return fail(I2LQR_ERR_INVALID, "\"lane_barrier_cost\" is 1 (on), or -1 / 0 (off)");
+    if (v == 1) {
+      if (problem_major(h))
+        return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_barrier_cost\" is built for the batch-minor / "
+                    "batch-tiled layouts: a problem-major handle takes \"barrier_cost\" (the "
+                    "one-problem-per-wavefront kernel)");
+      if (!h->lane_models)
+        return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_barrier_cost\" runs on the kernel of "
+                    "\"lane_models\": set \"lane_models\" to 1 first");
+      if (int rc = refuse_lane_model(h, "\"lane_barrier_cost\"")) return rc;
+    }
+    h->lane_barrier_cost = v == 1;
   }
   else if (!strcmp(name, "wave_chain")) {
     if (v != -1 && v != 0 && v != 1)
@@ -684,6 +706,7 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
     if (h->cfg.system_id == I2LQR_SYS_QUAD12) return "k_lane_iterate_rows";
     // a model of "lane_models": the launcher's own decision (LaneLaunch::names_model)
     switch (dispatch(h, [&](auto L) { return L.names_model(h); })) {
+      case 3: return "k_lane_iterate (barrier cost)";
       case 2: return "k_lane_iterate (state box)";
       case 1: return "k_lane_iterate (several obstacles)";
       default: break;

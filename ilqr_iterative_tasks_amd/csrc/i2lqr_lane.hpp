@@ -269,6 +269,11 @@ constexpr bool kRowsNTAll = I2LQR_ROWS_NT_ALL != 0;  // experiment: every row ac
 struct NoModel {
   static constexpr bool kOn = false;
 };
+// LaneWorker::forward's MERIT parameter when the barrier penalty is not wanted: every `if constexpr
+// (MERIT::kOn)` of the pass is discarded (the penalty itself: LaneMeritHook, i2lqr_lane_merit.hpp)
+struct NoMerit {
+  static constexpr bool kOn = false;
+};
 
 template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
   static constexpr int n = Sys::n, m = Sys::m, W = n + m, NT = Sys::NTRIG, NV = Sys::NVAR,
@@ -1593,9 +1598,13 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
   // D: horizon steps between the loads of a step's inputs and their use (D register sets that take
   // turns).  A step is ~700 cycles of arithmetic and a load from HBM / the far L2 takes 1500-2000:
   // with D = 1 the pass runs at the memory latency, not at the issue rate.
-  template <bool REROLL, bool WRITEX = true, int D = (DEEP ? 2 : 1)>
+  // MERIT ("lane_barrier_cost"): the barrier penalty of the candidate goes to *pen - the terms of
+  // step t from the x_t and the clipped u_t the step holds in registers, then those of x_N, into an
+  // accumulator of its own: nothing of it feeds x_{t+1} or the returned barrier-free cost.
+  template <bool REROLL, bool WRITEX = true, int D = (DEEP ? 2 : 1), class MERIT = NoMerit>
   __device__ __forceinline__ T forward(const T* X, const T* U, const T* gK, const T* gk, T* Xn,
-                                       T* Un, const T (&xT)[n]) const {
+                                       T* Un, const T (&xT)[n], const MERIT& mh = MERIT(),
+                                       T* pen = nullptr) const {
     T x[n], u[m], xn[n], tr[NT];
     T xo[n];
 #pragma unroll
@@ -1605,6 +1614,7 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
       if (WRITEX && Xn != X) at(Xn, rx(i, 0)) = x[i];
     }
     T cost = T(0);
+    [[maybe_unused]] T p = T(0);
     // The nominal state / input / gains of a step are consumed at its very start (the feedback
     // law); the loads for step t+D are issued right after, into the same registers, so the HBM
     // latency hides under the rest of the serial step(s).
@@ -1669,6 +1679,7 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
         for (int i = 0; i < n; i++) at(Xn, rx(i, t + 1)) = xn[i];
       }
       cost = cost + stage_cost(x, xT, u);
+      if constexpr (MERIT::kOn) p += mh.step_terms(*this, x, u, t);
 #pragma unroll
       for (int i = 0; i < n; i++) x[i] = xn[i];
     };
@@ -1691,6 +1702,7 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
       for (int t = 0; t < N; t++) body(t, xl[0], ul[0], kl[0]);
     }
     cost = cost + terminal_cost(x, xT);
+    if constexpr (MERIT::kOn) *pen = p + mh.state_terms(*this, x, N);
     return cost;
   }
 

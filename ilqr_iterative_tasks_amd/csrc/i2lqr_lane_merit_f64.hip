@@ -1,0 +1,7 @@
+// The bicycles' one-problem-per-lane kernel with the barrier cost (i2lqr_lane_merit.hpp) in fp64: a
+// translation unit of its own, so that the kernels of the other lane units stay as they are.
+#include "i2lqr_lane_merit.hpp"
+
+namespace i2lqr {
+I2LQR_LANE_MERIT_KERNELS(template __global__, double)
+}  // namespace i2lqr

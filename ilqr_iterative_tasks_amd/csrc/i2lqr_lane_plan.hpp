@@ -171,10 +171,13 @@ inline LaneOptions lane_options(const DeviceGeometry& g, const LaneShape& s, con
 
 // The opt-in models of a lane handle ("lane_models" 1; k_lane_iterate_model, i2lqr_lane_model.hpp):
 // `records` obstacle records per problem and the state box, both in the backward pass's derivatives.
+// `barrier_cost` ("lane_barrier_cost" 1): the accept / reject step sees the barriers
+// (k_lane_iterate_merit, i2lqr_lane_merit.hpp); one record and no box are a model then.
 struct LaneModel {
   int records = 1;   // "obstacles": 2 ... I2LQR_MAX_OBSTACLES; 1: off
   bool box = false;  // i2lqr_set_state_box with a finite bound
-  bool on() const { return records > 1 || box; }
+  bool barrier_cost = false;  // (the penalty is summed in registers: no LDS, the plan is the same)
+  bool on() const { return records > 1 || box || barrier_cost; }
 };
 // LDS of a model launch behind the gain steps and k_0: records 1 ... K - 1 of 64 lanes, six words
 // each, staged once per launch (record 0 stays in registers as in k_lane_iterate; the box is a

@@ -166,8 +166,12 @@ class BatchedILQR:
         them on k_lane_iterate_model, one problem per lane; `obs` is then [6, K, B] batch-minor /
         [B/64, 6, K, 64] batch-tiled, which shape("obs", B) and to_native() of a [B, K, 6] tensor give;
         solve() is then a single launch whatever set_compaction() says; 0 off, refused while a
-        model is on).  All but "wave_tail", "group_lanes", "line_search", "obstacles" and
-        "barrier_cost" leave the results bit-identical."""
+        model is on), "lane_barrier_cost" (with "lane_models" 1 only; 1: "barrier_cost"'s merit
+        J = c + P in the accept / reject step and the convergence test of the one-problem-per-lane
+        kernel, on k_lane_iterate_merit - every iterate() / solve() of the solver, a single launch,
+        `cost` returns J; a box that is off and one record are valid; 0 off; "lane_models" cannot
+        be switched off while it is on).  All but "wave_tail", "group_lanes", "line_search",
+        "obstacles", "barrier_cost" and "lane_barrier_cost" leave the results bit-identical."""
         self._check(self.lib.i2lqr_set_option(self._handle, name.encode(), int(value)))
         if name == "obstacles":
             self.obstacles = int(value) if int(value) > 1 else 1

@@ -403,11 +403,12 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     "lds_gain_steps" and "stagger" apply and preserve the results bit for bit.
  *                     i2lqr_iterate_pick takes its unfused form; i2lqr_backward answers
  *                     I2LQR_ERR_UNSUPPORTED while a model is on.  Still I2LQR_ERR_UNSUPPORTED with
- *                     "lane_models" 1: "line_search" > 1, "barrier_cost" 1 and "wave_chain" 1 on such
+ *                     "lane_models" 1: "line_search" > 1, "barrier_cost" 1 (such a handle has
+ *                     "lane_barrier_cost", below) and "wave_chain" 1 on such
  *                     a handle, and a model on quad12 (its row-block kernel has none).  With no
  *                     model set the handle runs what it ran before.  -1 or 0: off (the default);
- *                     I2LQR_ERR_INVALID while "obstacles" > 1 or a box is on (the message names what
- *                     to clear first).  Any other value is I2LQR_ERR_INVALID; a problem-major handle
+ *                     I2LQR_ERR_INVALID while "obstacles" > 1, a box or "lane_barrier_cost" is on (the
+ *                     message names what to clear first).  Any other value is I2LQR_ERR_INVALID; a problem-major handle
  *                     answers I2LQR_ERR_UNSUPPORTED to 1 (it has the one-problem-per-wavefront
  *                     kernels) and accepts 0 / -1.
  *   "wave_chain"      1: where i2lqr_solve_chained would answer I2LQR_ERR_UNSUPPORTED on this
@@ -459,7 +460,33 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     "wave_chain" (the chain kernels have no barrier cost: a launch per chain step
  *                     instead), and so does a forced "group_lanes" 8 or 16.  -1 or 0: off (the
  *                     default: nothing changes).  Any other value is I2LQR_ERR_INVALID; a batch-minor
- *                     / batch-tiled handle answers I2LQR_ERR_UNSUPPORTED to 1.
+ *                     / batch-tiled handle answers I2LQR_ERR_UNSUPPORTED to 1 (the message names
+ *                     "lane_barrier_cost").
+ *   "lane_barrier_cost"  batch-minor / batch-tiled handles of the bicycles whose "lane_models" is 1.
+ *                     1: the accept / reject step of the one-problem-per-lane kernel sees the merit
+ *                     J = c + P with the semantics written under "barrier_cost", word for word: P(X, U)
+ *                     on the clipped inputs and the rolled-out states, accept iff J_new is finite and
+ *                     J_new < J with the lamb schedule unchanged, converged iff accepted and
+ *                     |(J_new - J) / c| < eps with c the barrier-free cost of the nominal being
+ *                     replaced, cost[] = J of the returned trajectory, a non-finite J ends as status
+ *                     4, the fp32 overflow note.  There is one step size: no argmin over j.  P sums
+ *                     the handle's "obstacles" records and its state box; a box that is off and one
+ *                     record are valid (the merit is then c plus the input barriers plus the
+ *                     record's barrier).  EVERY i2lqr_iterate / i2lqr_solve of the handle runs
+ *                     k_lane_iterate_merit - k_lane_iterate_model with this accept step, the penalty
+ *                     summed inside its forward pass from registers (no LDS of its own) - under
+ *                     "lane_models"'s contract: i2lqr_solve is ONE launch with early exit;
+ *                     i2lqr_set_compaction, "helper_wavefront", "checkpoint_states" and
+ *                     "state_buffers" have no effect; "defer_states", "reroll_nominal",
+ *                     "merge_inputs", "lds_gain_steps" and "stagger" apply and preserve the results
+ *                     bit for bit; i2lqr_iterate_pick takes its unfused form (cost[] is J).
+ *                     i2lqr_backward has no accept step and is not concerned (it still answers
+ *                     I2LQR_ERR_UNSUPPORTED while "obstacles" > 1 or a box is on).  -1 or 0: off (the
+ *                     default: nothing changes), accepted on every handle.  Any other value is
+ *                     I2LQR_ERR_INVALID.  I2LQR_ERR_UNSUPPORTED to 1: a problem-major handle (use
+ *                     "barrier_cost" there), a lane handle whose "lane_models" is not 1, quad12.
+ *                     "lane_models" 0 while this option is on is I2LQR_ERR_INVALID: switch
+ *                     "lane_barrier_cost" off first.
  *   "stagger"         lane layouts (k_lane_iterate_rows, k_lane_iterate): every second half-thousand
  *                     of workgroups starts value x ~8000 cycles late, so that half of the
  *                     wavefronts stream their gains (forward pass) while the other half computes
@@ -505,7 +532,8 @@ int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, dou
  * lanes)", "k_group_iterate (workspace form)", "k_group_spec", "k_group_spec (sixteen lanes)",
  * "k_quad_iterate", "k_lane_iterate", "k_lane_iterate_pair" (the helper-wavefront form),
  * "k_lane_iterate (several obstacles)", "k_lane_iterate (state box)" (k_lane_iterate_model with
- * "lane_models" 1: the box takes precedence),
+ * "lane_models" 1: the box takes precedence), "k_lane_iterate (barrier cost)"
+ * (k_lane_iterate_merit with "lane_barrier_cost" 1: it ranks above the box),
  * "k_lane_iterate_rows"; "unsupported" if a forced option cannot be honoured and the launch would
  * return I2LQR_ERR_UNSUPPORTED: what to look for in a rocprofv3 kernel trace.  The name comes from
  * the launcher's own decision code run on scratch arguments, not from a copy of its conditions.

@@ -1,0 +1,156 @@
+"""CPU suite of "lane_barrier_cost" (include/i2lqr.h): the runs test_gpu_lane_barrier_cost.py makes
+on k_lane_iterate_merit meet the conditioning rule of the barrier-cost suite on the host reference,
+the option matters on them, the launch plan does not depend on it (i2lqr_lane_plan.hpp in a
+stand-alone program under AddressSanitizer and UBSan, as test_lane_models_host.py builds one), and
+the header, the C-ABI unit and the unit list name what they must."""
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from helpers import ST_LAMB_OVERFLOW
+from lane_merit_cases import (IDS, LAMB_OVERFLOW_EXITS, LANE_MERIT_RUNS, LANE_MERIT_TERMINATION_RUNS,
+                              LANE_MERIT_TILED, TERMINATION_IDS, lane_merit_reference)
+from opt_in_cases import MARGIN, MAX_LEFT_OUT, make_case
+from opt_in_reference import reference
+
+ROOT = Path(__file__).resolve().parent.parent
+CSRC = ROOT / "ilqr_iterative_tasks_amd" / "csrc"
+
+
+@pytest.mark.parametrize("case,n_iters,layout", LANE_MERIT_RUNS, ids=IDS)
+def test_gpu_runs_meet_the_conditioning_rule(case, n_iters, layout):
+    """A problem is compared on the GPU only if its smallest deciding margin is >= 1e-7 (ten times
+    the 1e-8 allowed on X and U).  A fixed-count run may leave out no problem, a termination run at
+    most 20 %."""
+    margin = lane_merit_reference(case, n_iters, layout)["margin"]
+    out = (margin < MARGIN).mean()
+    print(f"{case}: smallest margin {margin.min():.3g}, {out:.1%} of the problems below {MARGIN}")
+    assert out <= MAX_LEFT_OUT[n_iters is None]
+
+
+def test_the_unboxed_gpu_run_meets_the_conditioning_rule():
+    """test_gpu_lane_barrier_cost.py's run without a box (b4, one record, three iterations) asks for
+    80 %."""
+    cfg, host, _ = make_case("b4")
+    margin = reference(cfg, host, merit=True, max_iter=3, early_exit=False)["margin"]
+    print(f"smallest margin {margin.min():.3g}")
+    assert (margin >= MARGIN).mean() >= 0.8
+
+
+def test_the_long_horizon_gpu_run_meets_the_conditioning_rule():
+    """b4_N64 with its box, three iterations: branch words are compared on every problem."""
+    margin = lane_merit_reference("b4_N64", 3)["margin"]
+    print(f"smallest margin {margin.min():.3g}")
+    assert (margin >= MARGIN).all()
+
+
+@pytest.mark.parametrize("case,n_iters,layout", LANE_MERIT_TERMINATION_RUNS, ids=TERMINATION_IDS)
+def test_the_option_removes_lamb_overflow_exits(case, n_iters, layout):
+    """What the option is for: with the soft accept test more than a quarter of every set gives up
+    with LAMB_OVERFLOW; with the barrier cost fewer do (the README's figures, box on)."""
+    merit = lane_merit_reference(case, None, layout)
+    soft = lane_merit_reference(case, None, layout, merit=False)
+    exits = tuple(int((r["status"] == ST_LAMB_OVERFLOW).sum()) for r in (soft, merit))
+    print(f"{case}: LAMB_OVERFLOW exits {exits[0]} -> {exits[1]} of {len(soft['status'])}")
+    assert exits[1] < exits[0]
+    assert exits == LAMB_OVERFLOW_EXITS[case]
+
+
+@pytest.mark.parametrize("case", LANE_MERIT_TILED)
+def test_the_option_moves_lamb_on_the_tiled_sets(case):
+    merit = lane_merit_reference(case, None, 2)
+    soft = lane_merit_reference(case, None, 2, merit=False)
+    share = (merit["lamb"] != soft["lamb"]).mean()
+    print(f"{case}: lamb differs on {share:.2f} of the problems")
+    assert share >= 0.5
+
+
+PROGRAM = r"""
+#include "i2lqr_lane_plan.hpp"
+
+#include <cstdio>
+#include <initializer_list>
+
+using namespace i2lqr;
+
+static int bad = 0;
+#define CHECK(cond)                                              \
+  do {                                                           \
+    if (!(cond)) {                                               \
+      if (bad < 40) std::printf("FAILED line %d: %s\n", __LINE__, #cond); \
+      bad++;                                                     \
+    }                                                            \
+  } while (0)
+
+int main() {
+  const DeviceGeometry g;  // the MI355X figures
+  const LaneModel off;
+  CHECK(!off.on() && off.records == 1 && !off.box && !off.barrier_cost);
+  const LaneModel merit{1, false, true};  // one record, no box: the barrier cost alone is a model
+  CHECK(merit.on() && merit.barrier_cost);
+  CHECK((LaneModel{1, false, false}.on()) == false);
+  CHECK((LaneModel{3, false, false}.on()) && (LaneModel{1, true, false}.on()));
+  const int plants[2][2] = {{4, 2}, {6, 2}};
+  long combos = 0;
+  for (const auto& p : plants)
+    for (int word : {8, 4})
+      for (int N : {1, 20, 64})
+        for (int K : {1, 3, 8})
+          for (bool box : {false, true})
+            for (int64_t B : {(int64_t)1, (int64_t)64, (int64_t)4161, (int64_t)65536})
+              for (bool solve : {false, true})
+                for (int pin : {-1, 0, 1}) {
+                  const LaneShape s{p[0], p[1], N, word, false, false, 150};
+                  LaneTune t;
+                  t.opt_pair = pin;
+                  t.opt_ckpt = pin;
+                  t.compact_min_batch = 64;
+                  const LaneModel without{K, box, false}, with{K, box, true};
+                  CHECK(with.on());
+                  CHECK(lane_model_bytes(s, with) == lane_model_bytes(s, without));
+                  const LaneModelPlan a = lane_model_plan(g, s, t, without, B, solve);
+                  const LaneModelPlan b = lane_model_plan(g, s, t, with, B, solve);
+                  combos++;
+                  CHECK(a.model_bytes == b.model_bytes && a.lds == b.lds && a.fits == b.fits);
+                  CHECK(a.o.lds_steps == b.o.lds_steps);
+                  CHECK(!b.pair && !b.chunked && !a.pair && !a.chunked);
+                  CHECK(a.o.defer == b.o.defer && a.o.reroll == b.o.reroll && a.o.merge == b.o.merge &&
+                        a.o.stagger == b.o.stagger && a.o.ckpt == 0 && b.o.ckpt == 0);
+                  CHECK(b.model_bytes == (size_t)64 * 6 * (size_t)(K - 1) * (size_t)word);
+                }
+  CHECK(combos == 2L * 2 * 3 * 3 * 2 * 4 * 2 * 3);
+  std::printf("%d failed\n", bad);
+  return bad ? 1 : 0;
+}
+"""
+
+
+def test_lane_model_plan_does_not_depend_on_the_barrier_cost(tmp_path):
+    cxx = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    src = tmp_path / "lane_merit_plan_check.cpp"
+    src.write_text(PROGRAM)
+    exe = tmp_path / "lane_merit_plan_check"
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
+                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    print(run.stdout, run.stderr)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "0 failed" in run.stdout
+
+
+def test_header_sources_and_units_name_the_option():
+    hdr = (ROOT / "include" / "i2lqr.h").read_text()
+    assert '"lane_barrier_cost"' in hdr and '"k_lane_iterate (barrier cost)"' in hdr
+    assert "k_lane_iterate_merit" in hdr
+    src = (CSRC / "i2lqr_abi.hip").read_text()
+    assert '"k_lane_iterate (barrier cost)"' in src and '"lane_barrier_cost"' in src
+    units = subprocess.run(["make", "-s", "-C", str(CSRC), "units"], check=True, capture_output=True,
+                           text=True, timeout=60).stdout.split()
+    assert "i2lqr_lane_merit_f64" in units and "i2lqr_lane_merit_f32" in units
+    assert "i2lqr_lane_model_f64" in units and "i2lqr_lane_model_f32" in units
