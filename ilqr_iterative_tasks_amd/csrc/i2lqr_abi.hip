@@ -622,6 +622,9 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
     if (v != 1 && h->lane_barrier_cost)
       return fail(I2LQR_ERR_INVALID, "\"lane_models\" cannot be switched off while "
                   "\"lane_barrier_cost\" is on: set \"lane_barrier_cost\" to 0 first");
+    if (v != 1 && h->lane_line_search)
+      return fail(I2LQR_ERR_INVALID, "\"lane_models\" cannot be switched off while "
+                  "\"lane_line_search\" is on: set \"lane_line_search\" to 0 first");
     if (v != 1 && h->lane_models && (h->model.obs > 1 || h->model.box.on()))
       return fail(I2LQR_ERR_INVALID, "\"lane_models\" cannot be switched off while %s on: %s first",
                   h->model.box.on() ? "a state box is" : "\"obstacles\" is",
@@ -653,6 +656,22 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
       if (int rc = refuse_lane_model(h, "\"lane_barrier_cost\"")) return rc;
     }
     h->lane_barrier_cost = v == 1;
+  }
+  else if (!strcmp(name, "lane_line_search")) {
+    if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4 && v != 8)
+      return fail(I2LQR_ERR_INVALID, "\"lane_line_search\" is 2, 4 or 8 step sizes, or -1 / 0 / 1 "
+                  "(off)");
+    if (v > 1) {
+      if (problem_major(h))
+        return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_line_search\" is built for the batch-minor / "
+                    "batch-tiled layouts: a problem-major handle takes \"line_search\" (the "
+                    "one-problem-per-wavefront kernel)");
+      if (!h->lane_models)
+        return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_line_search\" runs on the kernel of "
+                    "\"lane_models\": set \"lane_models\" to 1 first");
+      if (int rc = refuse_lane_model(h, "\"lane_line_search\"")) return rc;
+    }
+    h->lane_line_search = v > 1 ? v : 0;
   }
   else if (!strcmp(name, "wave_chain")) {
     if (v != -1 && v != 0 && v != 1)
@@ -709,6 +728,7 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
       case 3: return "k_lane_iterate (barrier cost)";
       case 2: return "k_lane_iterate (state box)";
       case 1: return "k_lane_iterate (several obstacles)";
+      case 4: return "k_lane_iterate (line search)";
       default: break;
     }
     // the helper-wavefront form (both precisions, with or without stage weights): decided by the

@@ -30,6 +30,9 @@ struct i2lqr_handle {
   // "lane_barrier_cost" 1: every iterate / solve of the handle runs k_lane_iterate_merit (J = c + P in
   // the accept / reject step); only ever set while lane_models is
   bool lane_barrier_cost = false;
+  // "lane_line_search" 2 / 4 / 8: every iterate / solve of the handle runs k_lane_iterate_ls with that
+  // many step sizes (0: off); only ever set while lane_models is
+  int lane_line_search = 0;
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
   // it into its kernel, otherwise the call runs the separate kernels.  The pointer to the call's
   // epilogue is THREAD-LOCAL (t_epi in i2lqr_column_launch.hpp), not handle state: two host threads inside

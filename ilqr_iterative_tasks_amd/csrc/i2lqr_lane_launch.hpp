@@ -14,6 +14,7 @@
 #include "i2lqr_host.hpp"
 #include "i2lqr_kernels.h"
 #include "i2lqr_lane12.h"
+#include "i2lqr_lane_ls.hpp"
 #include "i2lqr_lane_merit.hpp"
 #include "i2lqr_lane_model.hpp"
 #include "i2lqr_lane_plan.hpp"
@@ -306,22 +307,24 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
   }
 
   // The opt-in models of the handle ("lane_models" 1: the records and the box h->model keeps; a lane
-  // handle without it never holds either; "lane_barrier_cost" 1 with or without them): what iterate()
-  // launches and what the names report.
+  // handle without it never holds either; "lane_barrier_cost" 1 and "lane_line_search" 2 / 4 / 8 with
+  // or without them): what iterate() launches and what the names report.
   static LaneModel model(const i2lqr_handle* h) {
-    return LaneModel{h->model.records(), h->model.box.on(), h->lane_barrier_cost};
+    return LaneModel{h->model.records(), h->model.box.on(), h->lane_barrier_cost,
+                     h->lane_line_search};
   }
   // 0: no model is on; 1: several obstacles; 2: the state box (it takes precedence, as on the
   // one-problem-per-wavefront side); 3: the barrier cost (above the box, as WAVE_MERIT ranks above
-  // WAVE_BOX) - i2lqr_iterate_kernel / i2lqr_solve_kernel
+  // WAVE_BOX); 4: the line search alone (below the others, as WAVE_LS) - i2lqr_iterate_kernel /
+  // i2lqr_solve_kernel
   static int names_model(const i2lqr_handle* h) {
     const LaneModel md = model(h);
-    return !md.on() ? 0 : md.barrier_cost ? 3 : md.box ? 2 : 1;
+    return !md.on() ? 0 : md.barrier_cost ? 3 : md.box ? 2 : md.records > 1 ? 1 : 4;
   }
   // i2lqr_iterate / i2lqr_solve with a model on: ONE launch of k_lane_iterate_model - with the barrier
-  // cost of k_lane_iterate_merit, same plan and same LDS - whatever the batch (a solve runs with early
-  // exit; "helper_wavefront", "checkpoint_states", "state_buffers" and i2lqr_set_compaction have no
-  // effect)
+  // cost of k_lane_iterate_merit, with the line search of k_lane_iterate_ls (soft or barrier cost), same
+  // plan and same LDS - whatever the batch (a solve runs with early exit; "helper_wavefront",
+  // "checkpoint_states", "state_buffers" and i2lqr_set_compaction have no effect)
   static int iterate_model(i2lqr_handle* h, const SolveIO& io, const LaneModel& md, hipStream_t s) {
     if constexpr (Sys::NBLK > 0) {
       return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_models\" is built for the bicycles' "
@@ -341,7 +344,17 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
       a.max_total = io.n_iters;
       const BoxCfg<T, n> box = make_box_cfg<T, n>(h->model.box);
       with_weights(c.flags, [&](auto W) {
-        if (md.barrier_cost) {
+        if (md.line_search > 1) {
+          const auto launch = [&](auto MERIT) {
+            grow_lds(h->geo, &k_lane_iterate_ls<T, Sys, W, TILED, MERIT>, sh, a, grid(io.B),
+                     p.model_bytes);
+            hipLaunchKernelGGL((k_lane_iterate_ls<T, Sys, W, TILED, MERIT>), dim3(grid(io.B)),
+                               dim3(64), lane_lds(sh, a) + p.model_bytes, s, c, a, md.records, box,
+                               (T)h->model.box.q1, md.line_search);
+          };
+          if (md.barrier_cost) launch(std::true_type());
+          else launch(std::false_type());
+        } else if (md.barrier_cost) {
           grow_lds(h->geo, &k_lane_iterate_merit<T, Sys, W, TILED>, sh, a, grid(io.B), p.model_bytes);
           hipLaunchKernelGGL((k_lane_iterate_merit<T, Sys, W, TILED>), dim3(grid(io.B)), dim3(64),
                              lane_lds(sh, a) + p.model_bytes, s, c, a, md.records, box,

@@ -170,8 +170,15 @@ class BatchedILQR:
         J = c + P in the accept / reject step and the convergence test of the one-problem-per-lane
         kernel, on k_lane_iterate_merit - every iterate() / solve() of the solver, a single launch,
         `cost` returns J; a box that is off and one record are valid; 0 off; "lane_models" cannot
-        be switched off while it is on).  All but "wave_tail", "group_lanes", "line_search",
-        "obstacles", "barrier_cost" and "lane_barrier_cost" leave the results bit-identical."""
+        be switched off while it is on), "lane_line_search" (with "lane_models" 1 only; 2 / 4 / 8:
+        "line_search"'s step sizes 2^-j on the one-problem-per-lane kernel, on k_lane_iterate_ls -
+        one backward pass, the candidates rolled out from one stream of loads, the best of them
+        through the accept / reject step the solver has, soft or "lane_barrier_cost"'s; composes
+        with "obstacles", set_state_box() and "lane_barrier_cost", and one record without a box is
+        valid; every iterate() / solve() of the solver, a single launch; 0 / 1 off; "lane_models"
+        cannot be switched off while it is on; "line_search" itself stays refused on these layouts).
+        All but "wave_tail", "group_lanes", "line_search", "obstacles", "barrier_cost",
+        "lane_barrier_cost" and "lane_line_search" leave the results bit-identical."""
         self._check(self.lib.i2lqr_set_option(self._handle, name.encode(), int(value)))
         if name == "obstacles":
             self.obstacles = int(value) if int(value) > 1 else 1

@@ -403,11 +403,12 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     "lds_gain_steps" and "stagger" apply and preserve the results bit for bit.
  *                     i2lqr_iterate_pick takes its unfused form; i2lqr_backward answers
  *                     I2LQR_ERR_UNSUPPORTED while a model is on.  Still I2LQR_ERR_UNSUPPORTED with
- *                     "lane_models" 1: "line_search" > 1, "barrier_cost" 1 (such a handle has
- *                     "lane_barrier_cost", below) and "wave_chain" 1 on such
+ *                     "lane_models" 1: "line_search" > 1 and "barrier_cost" 1 (such a handle has
+ *                     "lane_line_search" and "lane_barrier_cost", below) and "wave_chain" 1 on such
  *                     a handle, and a model on quad12 (its row-block kernel has none).  With no
  *                     model set the handle runs what it ran before.  -1 or 0: off (the default);
- *                     I2LQR_ERR_INVALID while "obstacles" > 1, a box or "lane_barrier_cost" is on (the
+ *                     I2LQR_ERR_INVALID while "obstacles" > 1, a box, "lane_barrier_cost" or
+ *                     "lane_line_search" is on (the
  *                     message names what to clear first).  Any other value is I2LQR_ERR_INVALID; a problem-major handle
  *                     answers I2LQR_ERR_UNSUPPORTED to 1 (it has the one-problem-per-wavefront
  *                     kernels) and accepts 0 / -1.
@@ -487,6 +488,37 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     "barrier_cost" there), a lane handle whose "lane_models" is not 1, quad12.
  *                     "lane_models" 0 while this option is on is I2LQR_ERR_INVALID: switch
  *                     "lane_barrier_cost" off first.
+ *   "lane_line_search"  batch-minor / batch-tiled handles of the bicycles whose "lane_models" is 1.
+ *                     2, 4 or 8: the forward pass of the one-problem-per-lane kernel tries that many
+ *                     step sizes alpha_j = 2^-j per iteration, with the semantics written under
+ *                     "line_search": one backward pass, candidate j rolls out
+ *                     u_t = clip(U_t + 2^-j k_t + K_t (x_t^j - X_t)) (the product is exact), the
+ *                     winner is argmin_j J_j (a NaN counts as +inf, ties go to the smallest j, j = 0 if
+ *                     every J is NaN) and goes through the accept / reject step the handle has: J = c
+ *                     and the soft test of k_lane_iterate_model, or with "lane_barrier_cost" 1 the
+ *                     merit J = c + P and its test, c and P carried separately.  The lamb schedule,
+ *                     the status words and cost[] do not change; K and k are returned unscaled.  It
+ *                     composes with "obstacles", the state box and "lane_barrier_cost"; one record,
+ *                     no box and no barrier cost are valid.  EVERY i2lqr_iterate / i2lqr_solve of the
+ *                     handle runs k_lane_iterate_ls: the nominal states, inputs and gains of a horizon
+ *                     step are loaded once and up to four candidate states advance from them in
+ *                     registers (8 step sizes: two passes of four; bicycle6 in fp64 with stage
+ *                     weights: passes of two), no candidate state is stored, and a second pass writes
+ *                     the inputs of a wavefront whose lanes chose j > 0.  Candidate 0 is computed
+ *                     with the arithmetic of the one-step kernels: a run in which no problem takes a
+ *                     short step returns the bits of the run with the option off.  No LDS and no
+ *                     workspace of its own, under "lane_models"'s contract: i2lqr_solve is ONE
+ *                     launch with early exit; i2lqr_set_compaction, "helper_wavefront",
+ *                     "checkpoint_states", "state_buffers" and "defer_states" (no pass stores states:
+ *                     an accepted step re-rolls them) have no effect; "reroll_nominal",
+ *                     "merge_inputs", "lds_gain_steps" and "stagger" apply; all of them preserve the
+ *                     results bit for bit.  i2lqr_iterate_pick takes its unfused form.  -1, 0 or 1:
+ *                     off (the default: the kernels and bits of before), accepted on every handle.
+ *                     Any other value is I2LQR_ERR_INVALID.  I2LQR_ERR_UNSUPPORTED to 2 / 4 / 8: a
+ *                     problem-major handle (use "line_search" there), a lane handle whose
+ *                     "lane_models" is not 1, quad12.  "lane_models" 0 while this option is on is
+ *                     I2LQR_ERR_INVALID: switch "lane_line_search" off first.  "line_search" itself
+ *                     stays I2LQR_ERR_UNSUPPORTED on these layouts.
  *   "stagger"         lane layouts (k_lane_iterate_rows, k_lane_iterate): every second half-thousand
  *                     of workgroups starts value x ~8000 cycles late, so that half of the
  *                     wavefronts stream their gains (forward pass) while the other half computes
@@ -534,6 +566,8 @@ int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, dou
  * "k_lane_iterate (several obstacles)", "k_lane_iterate (state box)" (k_lane_iterate_model with
  * "lane_models" 1: the box takes precedence), "k_lane_iterate (barrier cost)"
  * (k_lane_iterate_merit with "lane_barrier_cost" 1: it ranks above the box),
+ * "k_lane_iterate (line search)" (k_lane_iterate_ls with "lane_line_search" 2 / 4 / 8 and no other model: with one, the
+ * kernel is k_lane_iterate_ls and the name is that model's, as on the problem-major side),
  * "k_lane_iterate_rows"; "unsupported" if a forced option cannot be honoured and the launch would
  * return I2LQR_ERR_UNSUPPORTED: what to look for in a rocprofv3 kernel trace.  The name comes from
  * the launcher's own decision code run on scratch arguments, not from a copy of its conditions.
