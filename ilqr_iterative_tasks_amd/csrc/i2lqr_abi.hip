@@ -538,23 +538,14 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch) {
   return I2LQR_OK;
 }
 
-// The opt-in forms exist on the one-problem-per-wavefront kernel only: switching `what` on is refused
-// on a handle of another layout.
+// What the opt-in forms refuse, and in which words, is i2lqr_lane_opt_in.hpp's: the forms of the
+// one-problem-per-wavefront kernel on a handle of another layout (refuse_layout), and whatever
+// concerns the lane forms (lane_refusal).  Here an answer becomes the call's return value.
 static bool problem_major(const i2lqr_handle* h) { return h->cfg.layout == I2LQR_LAYOUT_PROBLEM_MAJOR; }
-static int refuse_layout(const char* what) {
-  return fail(I2LQR_ERR_UNSUPPORTED, "%s is built for the problem-major layout (the "
-              "one-problem-per-wavefront kernel)", what);
-}
-// ... but several obstacles and the state box, which a batch-minor / batch-tiled handle of the
-// bicycles takes with "lane_models" 1 (k_lane_iterate_model): 0 if `what` may be switched on
-static int refuse_lane_model(const i2lqr_handle* h, const char* what) {
-  if (problem_major(h)) return I2LQR_OK;
-  if (!h->lane_models) return refuse_layout(what);
-  if (h->cfg.system_id == I2LQR_SYS_QUAD12)
-    return fail(I2LQR_ERR_UNSUPPORTED, "%s with \"lane_models\" is built for the bicycles' "
-                "one-problem-per-lane kernel, not for quad12's row-block kernel "
-                "(k_lane_iterate_rows): use the problem-major layout", what);
-  return I2LQR_OK;
+static int refused(const LaneRefusal& r) { return r.code ? fail(r.code, "%s", r.text) : I2LQR_OK; }
+static int lane_ask(const i2lqr_handle* h, LaneAsk what, int v) {
+  return refused(lane_refusal(what, v, problem_major(h), h->cfg.system_id == I2LQR_SYS_QUAD12,
+                              h->model, h->lane_opt));
 }
 
 int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
@@ -601,82 +592,38 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   else if (!strcmp(name, "line_search")) {
     if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4 && v != 8)
       return fail(I2LQR_ERR_INVALID, "\"line_search\" is 2, 4 or 8 step sizes, or -1 / 0 / 1 (off)");
-    if (v > 1 && !problem_major(h)) return refuse_layout(wave_phrase(WAVE_LS));
+    if (v > 1 && !problem_major(h)) return refused(refuse_layout(wave_phrase(WAVE_LS)));
     h->model.ls = v > 1 ? v : 0;
   }
   else if (!strcmp(name, "obstacles")) {
     if (v > I2LQR_MAX_OBSTACLES)
       return fail(I2LQR_ERR_INVALID, "\"obstacles\" is 2 ... %d records per problem, or -1 / 0 / 1 "
                   "(off: one record)", I2LQR_MAX_OBSTACLES);
-    if (v > 1)
-      if (int rc = refuse_lane_model(h, wave_phrase(WAVE_OBS))) return rc;
+    if (int rc = lane_ask(h, LANE_ASK_OBSTACLES, v)) return rc;
     h->model.obs = v > 1 ? v : 0;
   }
   else if (!strcmp(name, "lane_models")) {
-    if (v != -1 && v != 0 && v != 1)
-      return fail(I2LQR_ERR_INVALID, "\"lane_models\" is 1 (on), or -1 / 0 (off)");
-    if (v == 1 && problem_major(h))
-      return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_models\" is built for the batch-minor / batch-tiled "
-                  "layouts (a problem-major handle runs the models on the one-problem-per-wavefront "
-                  "kernels without it)");
-    if (v != 1 && h->lane_barrier_cost)
-      return fail(I2LQR_ERR_INVALID, "\"lane_models\" cannot be switched off while "
-                  "\"lane_barrier_cost\" is on: set \"lane_barrier_cost\" to 0 first");
-    if (v != 1 && h->lane_line_search)
-      return fail(I2LQR_ERR_INVALID, "\"lane_models\" cannot be switched off while "
-                  "\"lane_line_search\" is on: set \"lane_line_search\" to 0 first");
-    if (v != 1 && h->lane_models && (h->model.obs > 1 || h->model.box.on()))
-      return fail(I2LQR_ERR_INVALID, "\"lane_models\" cannot be switched off while %s on: %s first",
-                  h->model.box.on() ? "a state box is" : "\"obstacles\" is",
-                  h->model.box.on() ? "clear it (i2lqr_set_state_box with NULL bounds)"
-                                    : "set \"obstacles\" to 1");
-    h->lane_models = v == 1;
+    if (int rc = lane_ask(h, LANE_ASK_MODELS, v)) return rc;
+    h->lane_opt.models = v == 1;
   }
   else if (!strcmp(name, "barrier_cost")) {
     if (v != -1 && v != 0 && v != 1)
       return fail(I2LQR_ERR_INVALID, "\"barrier_cost\" is 1 (on), or -1 / 0 (off)");
-    if (v == 1 && !problem_major(h))
-      return fail(I2LQR_ERR_UNSUPPORTED, "%s is built for the problem-major layout (the "
-                  "one-problem-per-wavefront kernel); a batch-minor / batch-tiled handle of the "
-                  "bicycles has \"lane_barrier_cost\" (with \"lane_models\" 1)",
-                  wave_phrase(WAVE_MERIT));
+    if (int rc = lane_ask(h, WAVE_ASK_BARRIER_COST, v)) return rc;
     h->model.barrier_cost = v == 1;
   }
   else if (!strcmp(name, "lane_barrier_cost")) {
-    if (v != -1 && v != 0 && v != 1)
-      return fail(I2LQR_ERR_INVALID, "\"lane_barrier_cost\" is 1 (on), or -1 / 0 (off)");
-    if (v == 1) {
-      if (problem_major(h))
-        return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_barrier_cost\" is built for the batch-minor / "
-                    "batch-tiled layouts: a problem-major handle takes \"barrier_cost\" (the "
-                    "one-problem-per-wavefront kernel)");
-      if (!h->lane_models)
-        return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_barrier_cost\" runs on the kernel of "
-                    "\"lane_models\": set \"lane_models\" to 1 first");
-      if (int rc = refuse_lane_model(h, "\"lane_barrier_cost\"")) return rc;
-    }
-    h->lane_barrier_cost = v == 1;
+    if (int rc = lane_ask(h, LANE_ASK_BARRIER_COST, v)) return rc;
+    h->lane_opt.barrier_cost = v == 1;
   }
   else if (!strcmp(name, "lane_line_search")) {
-    if (v != -1 && v != 0 && v != 1 && v != 2 && v != 4 && v != 8)
-      return fail(I2LQR_ERR_INVALID, "\"lane_line_search\" is 2, 4 or 8 step sizes, or -1 / 0 / 1 "
-                  "(off)");
-    if (v > 1) {
-      if (problem_major(h))
-        return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_line_search\" is built for the batch-minor / "
-                    "batch-tiled layouts: a problem-major handle takes \"line_search\" (the "
-                    "one-problem-per-wavefront kernel)");
-      if (!h->lane_models)
-        return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_line_search\" runs on the kernel of "
-                    "\"lane_models\": set \"lane_models\" to 1 first");
-      if (int rc = refuse_lane_model(h, "\"lane_line_search\"")) return rc;
-    }
-    h->lane_line_search = v > 1 ? v : 0;
+    if (int rc = lane_ask(h, LANE_ASK_LINE_SEARCH, v)) return rc;
+    h->lane_opt.line_search = v > 1 ? v : 0;
   }
   else if (!strcmp(name, "wave_chain")) {
     if (v != -1 && v != 0 && v != 1)
       return fail(I2LQR_ERR_INVALID, "\"wave_chain\" is 1 (on), or -1 / 0 (off)");
-    if (v == 1 && !problem_major(h)) return refuse_layout("\"wave_chain\"");
+    if (v == 1 && !problem_major(h)) return refused(refuse_layout("\"wave_chain\""));
     col.opt_wave_chain = v == 1 ? 1 : 0;
   }
   else if (!strcmp(name, "group_lanes")) {
@@ -713,8 +660,7 @@ int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, dou
       b.m_hi |= 1u << i;
     }
   }
-  if (b.on())
-    if (int rc = refuse_lane_model(h, wave_phrase(WAVE_BOX))) return rc;
+  if (int rc = lane_ask(h, LANE_ASK_BOX, b.on() ? 1 : 0)) return rc;
   h->model.box = b;
   return I2LQR_OK;
 }
@@ -723,14 +669,9 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
   if (!h) return "";
   if (h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR) {
     if (h->cfg.system_id == I2LQR_SYS_QUAD12) return "k_lane_iterate_rows";
-    // a model of "lane_models": the launcher's own decision (LaneLaunch::names_model)
-    switch (dispatch(h, [&](auto L) { return L.names_model(h); })) {
-      case 3: return "k_lane_iterate (barrier cost)";
-      case 2: return "k_lane_iterate (state box)";
-      case 1: return "k_lane_iterate (several obstacles)";
-      case 4: return "k_lane_iterate (line search)";
-      default: break;
-    }
+    // a form of "lane_models": what LaneLaunch::iterate launches from the same record
+    if (const LaneForm f = lane_model(h->model, h->lane_opt).form(); f != LANE_PLAIN)
+      return lane_kernel_name(f);
     // the helper-wavefront form (both precisions, with or without stage weights): decided by the
     // launcher's own rules (LaneLaunch::names_pair)
     const auto pair = [&](auto L) { return L.names_pair(h, B, early_exit ? 1 : 0); };

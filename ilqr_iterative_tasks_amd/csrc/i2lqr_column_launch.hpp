@@ -160,7 +160,6 @@ template <class T, class Sys> struct Launch {
     return I2LQR_OK;
   }
   static int names_pair(const i2lqr_handle*, int64_t, int) { return 0; }
-  static int names_model(const i2lqr_handle*) { return 0; }  // ("lane_models": the lane layouts')
   // io.B chains of k problems each in ONE launch (chain_plan)
   static int solve_chained(i2lqr_handle* h, const SolveIO& io, int k, hipStream_t s) {
     const ChainPlan plan = chain_plan(h->geo, h->fit, h->col, h->model.form(), registered_ws(h), io.B);

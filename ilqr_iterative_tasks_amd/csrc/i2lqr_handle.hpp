@@ -24,15 +24,10 @@ struct i2lqr_handle {
   i2lqr::ColumnTune col;  // options of the problem-major layout (i2lqr_column_plan.hpp)
   i2lqr::ColumnFit fit;   // what the kernel units know about cfg, filled in i2lqr_create
   i2lqr::WaveModel model;  // one-problem-per-wavefront kernel: "line_search", "obstacles" and the state box (i2lqr_set_state_box), all off by default (i2lqr_wave_model.hpp)
-  // "lane_models" 1: a batch-minor / batch-tiled handle accepts model.obs and model.box and runs them
-  // on k_lane_iterate_model (LaneLaunch::iterate_model); never set on a problem-major handle
-  bool lane_models = false;
-  // "lane_barrier_cost" 1: every iterate / solve of the handle runs k_lane_iterate_merit (J = c + P in
-  // the accept / reject step); only ever set while lane_models is
-  bool lane_barrier_cost = false;
-  // "lane_line_search" 2 / 4 / 8: every iterate / solve of the handle runs k_lane_iterate_ls with that
-  // many step sizes (0: off); only ever set while lane_models is
-  int lane_line_search = 0;
+  // "lane_models", "lane_barrier_cost", "lane_line_search": with `model`, what a batch-minor /
+  // batch-tiled handle runs on k_lane_iterate_model / _merit / _ls (lane_model(), i2lqr_lane_opt_in.hpp;
+  // LaneLaunch::iterate_model)
+  i2lqr::LaneOptIn lane_opt;
   // i2lqr_iterate_pick: the epilogue a call asks for; `fused` is set by the launcher that folded
   // it into its kernel, otherwise the call runs the separate kernels.  The pointer to the call's
   // epilogue is THREAD-LOCAL (t_epi in i2lqr_column_launch.hpp), not handle state: two host threads inside

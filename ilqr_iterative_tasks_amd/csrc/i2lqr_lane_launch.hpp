@@ -306,30 +306,13 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     return I2LQR_OK;
   }
 
-  // The opt-in models of the handle ("lane_models" 1: the records and the box h->model keeps; a lane
-  // handle without it never holds either; "lane_barrier_cost" 1 and "lane_line_search" 2 / 4 / 8 with
-  // or without them): what iterate() launches and what the names report.
-  static LaneModel model(const i2lqr_handle* h) {
-    return LaneModel{h->model.records(), h->model.box.on(), h->lane_barrier_cost,
-                     h->lane_line_search};
-  }
-  // 0: no model is on; 1: several obstacles; 2: the state box (it takes precedence, as on the
-  // one-problem-per-wavefront side); 3: the barrier cost (above the box, as WAVE_MERIT ranks above
-  // WAVE_BOX); 4: the line search alone (below the others, as WAVE_LS) - i2lqr_iterate_kernel /
-  // i2lqr_solve_kernel
-  static int names_model(const i2lqr_handle* h) {
-    const LaneModel md = model(h);
-    return !md.on() ? 0 : md.barrier_cost ? 3 : md.box ? 2 : md.records > 1 ? 1 : 4;
-  }
   // i2lqr_iterate / i2lqr_solve with a model on: ONE launch of k_lane_iterate_model - with the barrier
   // cost of k_lane_iterate_merit, with the line search of k_lane_iterate_ls (soft or barrier cost), same
   // plan and same LDS - whatever the batch (a solve runs with early exit; "helper_wavefront",
   // "checkpoint_states", "state_buffers" and i2lqr_set_compaction have no effect)
   static int iterate_model(i2lqr_handle* h, const SolveIO& io, const LaneModel& md, hipStream_t s) {
     if constexpr (Sys::NBLK > 0) {
-      return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_models\" is built for the bicycles' "
-                  "one-problem-per-lane kernel, not for the row-block kernel of this plant "
-                  "(k_lane_iterate_rows): use the problem-major layout");
+      return fail(I2LQR_ERR_UNSUPPORTED, "%s", lane_models_rows_text());
     } else {
       if (int rc = need_ws(h, io.B)) return rc;
       const LaneShape sh = shape(h);
@@ -343,27 +326,22 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
       set_io(a, io.n_iters, io.early_exit, user_set(io));
       a.max_total = io.n_iters;
       const BoxCfg<T, n> box = make_box_cfg<T, n>(h->model.box);
+      // one launch expression: the kernel's address and what follows c, a, md.records and box
+      const auto launch = [&](auto kernel, auto... tail) {
+        grow_lds(h->geo, kernel, sh, a, grid(io.B), p.model_bytes);
+        hipLaunchKernelGGL(kernel, dim3(grid(io.B)), dim3(64), lane_lds(sh, a) + p.model_bytes, s,
+                           c, a, md.records, box, tail...);
+      };
+      const T box_q1 = (T)h->model.box.q1;
       with_weights(c.flags, [&](auto W) {
-        if (md.line_search > 1) {
-          const auto launch = [&](auto MERIT) {
-            grow_lds(h->geo, &k_lane_iterate_ls<T, Sys, W, TILED, MERIT>, sh, a, grid(io.B),
-                     p.model_bytes);
-            hipLaunchKernelGGL((k_lane_iterate_ls<T, Sys, W, TILED, MERIT>), dim3(grid(io.B)),
-                               dim3(64), lane_lds(sh, a) + p.model_bytes, s, c, a, md.records, box,
-                               (T)h->model.box.q1, md.line_search);
-          };
-          if (md.barrier_cost) launch(std::true_type());
-          else launch(std::false_type());
-        } else if (md.barrier_cost) {
-          grow_lds(h->geo, &k_lane_iterate_merit<T, Sys, W, TILED>, sh, a, grid(io.B), p.model_bytes);
-          hipLaunchKernelGGL((k_lane_iterate_merit<T, Sys, W, TILED>), dim3(grid(io.B)), dim3(64),
-                             lane_lds(sh, a) + p.model_bytes, s, c, a, md.records, box,
-                             (T)h->model.box.q1);
-        } else {
-          grow_lds(h->geo, &k_lane_iterate_model<T, Sys, W, TILED>, sh, a, grid(io.B), p.model_bytes);
-          hipLaunchKernelGGL((k_lane_iterate_model<T, Sys, W, TILED>), dim3(grid(io.B)), dim3(64),
-                             lane_lds(sh, a) + p.model_bytes, s, c, a, md.records, box);
-        }
+        if (md.line_search > 1 && md.barrier_cost)
+          launch(&k_lane_iterate_ls<T, Sys, W, TILED, true>, box_q1, md.line_search);
+        else if (md.line_search > 1)
+          launch(&k_lane_iterate_ls<T, Sys, W, TILED, false>, box_q1, md.line_search);
+        else if (md.barrier_cost)
+          launch(&k_lane_iterate_merit<T, Sys, W, TILED>, box_q1);
+        else
+          launch(&k_lane_iterate_model<T, Sys, W, TILED>);
       });
       HIP_TRY(hipGetLastError());
       return I2LQR_OK;
@@ -371,7 +349,8 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
   }
 
   static int iterate(i2lqr_handle* h, const SolveIO& io, hipStream_t s) {
-    if (const LaneModel md = model(h); md.on()) return iterate_model(h, io, md, s);
+    if (const LaneModel md = lane_model(h->model, h->lane_opt); md.on())
+      return iterate_model(h, io, md, s);
     const LaneShape sh = shape(h);
     const bool solve = io.early_exit && io.n_iters == h->cfg.max_iter;
     if (solve && chunked(h->geo, sh, h->lane, io.B)) return solve_compacting(h, io, s);

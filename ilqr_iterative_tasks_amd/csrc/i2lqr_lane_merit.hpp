@@ -224,22 +224,9 @@ k_lane_iterate_merit(const DevCfg<T, Sys::n, Sys::m> c, const LaneArgs<T> a, con
   if (a.status) a.status[b] = status;
 }
 
-// The sixteen instantiations (two bicycles x two precisions x stage weights x lane layout):
-// `extern template` for the launcher, the instantiations in the two units
-#define I2LQR_LANE_MERIT_KERNELS_(DECL, REAL, SYS, N_, M_, QR, TL)                                 \
-  DECL void k_lane_iterate_merit<REAL, SYS<REAL>, QR, TL>(                                         \
-      const DevCfg<REAL, N_, M_>, const LaneArgs<REAL>, const int, const BoxCfg<REAL, N_>,         \
-      const REAL);
-#define I2LQR_LANE_MERIT_BICYCLE_(DECL, REAL, SYS, N_, M_)                                         \
-  I2LQR_LANE_MERIT_KERNELS_(DECL, REAL, SYS, N_, M_, false, false)                                 \
-  I2LQR_LANE_MERIT_KERNELS_(DECL, REAL, SYS, N_, M_, false, true)                                  \
-  I2LQR_LANE_MERIT_KERNELS_(DECL, REAL, SYS, N_, M_, true, false)                                  \
-  I2LQR_LANE_MERIT_KERNELS_(DECL, REAL, SYS, N_, M_, true, true)
-#define I2LQR_LANE_MERIT_KERNELS(DECL, REAL)                                                       \
-  I2LQR_LANE_MERIT_BICYCLE_(DECL, REAL, Bicycle4, 4, 2)                                            \
-  I2LQR_LANE_MERIT_BICYCLE_(DECL, REAL, Bicycle6, 6, 2)
-
-I2LQR_LANE_MERIT_KERNELS(extern template __global__, double)
-I2LQR_LANE_MERIT_KERNELS(extern template __global__, float)
+// The sixteen instantiations (I2LQR_LANE_OPT_KERNELS, i2lqr_lane_model.hpp): `extern template` for
+// the launcher, the instantiations in the two units
+I2LQR_LANE_OPT_KERNELS(extern template __global__, k_lane_iterate_merit, I2LQR_LANE_TAIL_MERIT, double)
+I2LQR_LANE_OPT_KERNELS(extern template __global__, k_lane_iterate_merit, I2LQR_LANE_TAIL_MERIT, float)
 
 }  // namespace i2lqr

@@ -3,5 +3,5 @@
 #include "i2lqr_lane_merit.hpp"
 
 namespace i2lqr {
-I2LQR_LANE_MERIT_KERNELS(template __global__, double)
+I2LQR_LANE_OPT_KERNELS(template __global__, k_lane_iterate_merit, I2LQR_LANE_TAIL_MERIT, double)
 }  // namespace i2lqr

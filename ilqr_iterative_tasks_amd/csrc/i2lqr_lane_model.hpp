@@ -175,21 +175,24 @@ k_lane_iterate_model(const DevCfg<T, Sys::n, Sys::m> c, const LaneArgs<T> a, con
   if (a.status) a.status[b] = status;
 }
 
-// The sixteen instantiations (two bicycles x two precisions x stage weights x lane layout):
-// `extern template` for the launcher, the instantiations in the two units
-#define I2LQR_LANE_MODEL_KERNELS_(DECL, REAL, SYS, N_, M_, QR, TL)                                 \
-  DECL void k_lane_iterate_model<REAL, SYS<REAL>, QR, TL>(                                         \
-      const DevCfg<REAL, N_, M_>, const LaneArgs<REAL>, const int, const BoxCfg<REAL, N_>);
-#define I2LQR_LANE_MODEL_BICYCLE_(DECL, REAL, SYS, N_, M_)                                         \
-  I2LQR_LANE_MODEL_KERNELS_(DECL, REAL, SYS, N_, M_, false, false)                                 \
-  I2LQR_LANE_MODEL_KERNELS_(DECL, REAL, SYS, N_, M_, false, true)                                  \
-  I2LQR_LANE_MODEL_KERNELS_(DECL, REAL, SYS, N_, M_, true, false)                                  \
-  I2LQR_LANE_MODEL_KERNELS_(DECL, REAL, SYS, N_, M_, true, true)
-#define I2LQR_LANE_MODEL_KERNELS(DECL, REAL)                                                       \
-  I2LQR_LANE_MODEL_BICYCLE_(DECL, REAL, Bicycle4, 4, 2)                                            \
-  I2LQR_LANE_MODEL_BICYCLE_(DECL, REAL, Bicycle6, 6, 2)
+// The sixteen instantiations of KERNEL (two bicycles x two precisions x stage weights x lane layout);
+// TAIL(REAL) spells the parameter types that follow DevCfg, LaneArgs, the record count and the box.
+// Expanded as `extern template` for the launcher, in the kernel's two units as the instantiations.
+#define I2LQR_LANE_TAIL_MODEL(REAL)
+#define I2LQR_LANE_TAIL_MERIT(REAL) , const REAL
+#define I2LQR_LANE_OPT_KERNELS_(DECL, KERNEL, TAIL, REAL, SYS, N_, M_, QR, TL)                     \
+  DECL void KERNEL<REAL, SYS<REAL>, QR, TL>(const DevCfg<REAL, N_, M_>, const LaneArgs<REAL>,      \
+                                            const int, const BoxCfg<REAL, N_> TAIL(REAL));
+#define I2LQR_LANE_OPT_BICYCLE_(DECL, KERNEL, TAIL, REAL, SYS, N_, M_)                             \
+  I2LQR_LANE_OPT_KERNELS_(DECL, KERNEL, TAIL, REAL, SYS, N_, M_, false, false)                     \
+  I2LQR_LANE_OPT_KERNELS_(DECL, KERNEL, TAIL, REAL, SYS, N_, M_, false, true)                      \
+  I2LQR_LANE_OPT_KERNELS_(DECL, KERNEL, TAIL, REAL, SYS, N_, M_, true, false)                      \
+  I2LQR_LANE_OPT_KERNELS_(DECL, KERNEL, TAIL, REAL, SYS, N_, M_, true, true)
+#define I2LQR_LANE_OPT_KERNELS(DECL, KERNEL, TAIL, REAL)                                           \
+  I2LQR_LANE_OPT_BICYCLE_(DECL, KERNEL, TAIL, REAL, Bicycle4, 4, 2)                                \
+  I2LQR_LANE_OPT_BICYCLE_(DECL, KERNEL, TAIL, REAL, Bicycle6, 6, 2)
 
-I2LQR_LANE_MODEL_KERNELS(extern template __global__, double)
-I2LQR_LANE_MODEL_KERNELS(extern template __global__, float)
+I2LQR_LANE_OPT_KERNELS(extern template __global__, k_lane_iterate_model, I2LQR_LANE_TAIL_MODEL, double)
+I2LQR_LANE_OPT_KERNELS(extern template __global__, k_lane_iterate_model, I2LQR_LANE_TAIL_MODEL, float)
 
 }  // namespace i2lqr

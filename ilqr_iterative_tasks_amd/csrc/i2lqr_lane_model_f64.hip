@@ -3,5 +3,5 @@
 #include "i2lqr_lane_model.hpp"
 
 namespace i2lqr {
-I2LQR_LANE_MODEL_KERNELS(template __global__, double)
+I2LQR_LANE_OPT_KERNELS(template __global__, k_lane_iterate_model, I2LQR_LANE_TAIL_MODEL, double)
 }  // namespace i2lqr

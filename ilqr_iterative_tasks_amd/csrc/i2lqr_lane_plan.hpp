@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "i2lqr_geometry.hpp"
+#include "i2lqr_lane_opt_in.hpp"
 
 namespace i2lqr {
 
@@ -169,22 +170,9 @@ inline LaneOptions lane_options(const DeviceGeometry& g, const LaneShape& s, con
   return o;
 }
 
-// The opt-in models of a lane handle ("lane_models" 1; k_lane_iterate_model, i2lqr_lane_model.hpp):
-// `records` obstacle records per problem and the state box, both in the backward pass's derivatives.
-// `barrier_cost` ("lane_barrier_cost" 1): the accept / reject step sees the barriers
-// (k_lane_iterate_merit, i2lqr_lane_merit.hpp); one record and no box are a model then.
-// `line_search` ("lane_line_search" 2 / 4 / 8): that many step sizes per iteration
-// (k_lane_iterate_ls, i2lqr_lane_ls.hpp), with or without any of the others.
-struct LaneModel {
-  int records = 1;   // "obstacles": 2 ... I2LQR_MAX_OBSTACLES; 1: off
-  bool box = false;  // i2lqr_set_state_box with a finite bound
-  bool barrier_cost = false;  // (the penalty is summed in registers: no LDS, the plan is the same)
-  int line_search = 0;  // 2, 4, 8; 0: off (the candidates live in registers: no LDS, the plan is the same)
-  bool on() const { return records > 1 || box || barrier_cost || line_search > 1; }
-};
-// LDS of a model launch behind the gain steps and k_0: records 1 ... K - 1 of 64 lanes, six words
-// each, staged once per launch (record 0 stays in registers as in k_lane_iterate; the box is a
-// by-value kernel argument and takes none)
+// LDS of a model launch (LaneModel, i2lqr_lane_opt_in.hpp) behind the gain steps and k_0: records
+// 1 ... K - 1 of 64 lanes, six words each, staged once per launch (record 0 stays in registers as in
+// k_lane_iterate; the box is a by-value kernel argument and takes none)
 inline size_t lane_model_bytes(const LaneShape& s, const LaneModel& md) {
   return md.records > 1 ? (size_t)64 * 6 * (size_t)(md.records - 1) * (size_t)s.word : 0;
 }

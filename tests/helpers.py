@@ -162,6 +162,50 @@ def check_solve_outputs(solver, cfg, host, buf, early_exit=True, n_iters=None, r
     return {"x_err": x_err, "cost_err": c_err, "lamb_err": lamb_err}
 
 
+# What the stand-alone host programs of the *_host.py suites share: the text behind the #include of
+# the header under test (the headers' namespace, the failure counter and CHECK) ...
+HOST_CHECK_PRELUDE = r"""
+#include <cstdio>
+#include <cstring>
+#include <initializer_list>
+
+using namespace i2lqr;
+
+static int bad = 0;
+#define CHECK(cond)                                              \
+  do {                                                           \
+    if (!(cond)) {                                               \
+      if (bad < 40) std::printf("FAILED line %d: %s\n", __LINE__, #cond); \
+      bad++;                                                     \
+    }                                                            \
+  } while (0)
+"""
+
+
+def run_host_program(tmp_path, name, source, include_dirs):
+    """... and their build and run: `source` (a program with its own main that prints "<n> failed"
+    and returns 1 if n > 0) compiled as tmp_path/name with the host compiler under AddressSanitizer
+    and UBSan, warnings as errors, then run: exit status 0 and "0 failed"."""
+    import shutil
+    import subprocess
+
+    import pytest
+    cxx = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    src = tmp_path / f"{name}.cpp"
+    src.write_text(source)
+    exe = tmp_path / name
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    *(f"-I{d}" for d in include_dirs), "-o", str(exe), str(src)],
+                   check=True, capture_output=True, timeout=300)
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    print(run.stdout, run.stderr)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "0 failed" in run.stdout
+
+
 def problems_from_calls(g, N, n=4, m=2):
     """Golden ilqr() call records (x0, x_term, lamb_in, obs) -> problem-major host batch."""
     B = len(g["x0"])

@@ -6,16 +6,25 @@ K relative to the problem's largest gain, the feed-forward k relative to max(|k|
 converged solution, so it is compared at the scale of the input box, as
 test_gpu_parity.py::test_iterate_vs_oracle does.  Problems whose lamb differs from the reference's
 took another accept / reject branch and are left out; at least 97 % must remain."""
+import functools
+
 import numpy as np
 
-from helpers import TOL_SOLVE, batch_rel_err, dev_batch, to_host
-from opt_in_reference import OUTPUTS  # noqa: F401 (the suites take it from here)
+from helpers import ROLLOUT_TOL, TOL_SOLVE, batch_rel_err, dev_batch, to_host
+from lane_cases import lane_reference
+from opt_in_cases import make_case, on_layout
+from opt_in_reference import OUTPUTS, penalty  # noqa: F401 (the suites take OUTPUTS from here)
 
 # the kernels' display names (csrc/i2lqr_wave_model.hpp, csrc/i2lqr_abi.hip)
 LS_NAME = "k_iterate (line search)"
 OBS_NAME = "k_iterate (several obstacles)"
 BOX_NAME = "k_iterate (state box)"
 MERIT_NAME = "k_iterate (barrier cost)"
+# ... and those of the lane forms (csrc/i2lqr_lane_opt_in.hpp)
+LANE_LS_NAME = "k_lane_iterate (line search)"
+LANE_OBS_NAME = "k_lane_iterate (several obstacles)"
+LANE_BOX_NAME = "k_lane_iterate (state box)"
+LANE_MERIT_NAME = "k_lane_iterate (barrier cost)"
 
 
 def make_solver(cfg, box=None, barrier_cost=None, **options):
@@ -74,3 +83,103 @@ def compare(solver, buf, ref, n_iters, gains=True):
         assert batch_rel_err(to_host(solver, buf["K"])[same], ref["K"][same]) < 1e-7
         assert batch_rel_err(to_host(solver, buf["k"])[same], ref["k"][same], floor=1.0) < 1e-7
     return same
+
+
+# The lane forms ("lane_models", "lane_barrier_cost", "lane_line_search": k_lane_iterate_model / _merit
+# / _ls on a batch-minor (layout 1) or batch-tiled (2) handle)
+
+
+def records(host):
+    """K of obs[B, K, 6]; None for obs[B, 6] or no obstacle."""
+    return host["obs"].shape[1] if host["obs"] is not None and host["obs"].ndim == 3 else None
+
+
+def lane_solver(cfg, host=None, box=None, layout=1, A=1, merit=False, models=True, **options):
+    """A solver of cfg on a lane layout: the scheduling options, "lane_models", "obstacles" (given, or
+    for the records of `host`), "lane_barrier_cost", "lane_line_search" (A > 1), then the box."""
+    obstacles = options.pop("obstacles", None)
+    if models:
+        options["lane_models"] = 1
+    if obstacles is None and host is not None:
+        obstacles = records(host)
+    if obstacles:
+        options["obstacles"] = obstacles
+    if merit:
+        options["lane_barrier_cost"] = 1
+    if A > 1:
+        options["lane_line_search"] = A
+    return make_solver(on_layout(cfg, layout), box, **options)
+
+
+def lane_name(host, box=None, merit=False, A=1):
+    """The display name of that handle: barrier cost > box > obstacles > line search (LaneModel::form,
+    csrc/i2lqr_lane_opt_in.hpp); None with nothing on."""
+    if merit:
+        return LANE_MERIT_NAME
+    if box is not None and box.active:
+        return LANE_BOX_NAME
+    if records(host):
+        return LANE_OBS_NAME
+    return LANE_LS_NAME if A > 1 else None
+
+
+def checked_lane_solver(cfg, host, box=None, layout=1, A=1, merit=False, **options):
+    """lane_solver with a form on, both names asserted."""
+    solver = lane_solver(cfg, host, box, layout, A, merit, **options)
+    B = host["X"].shape[0]
+    assert solver.iterate_kernel(B) == solver.solve_kernel(B) == lane_name(host, box, merit, A)
+    return solver
+
+
+def check_outputs(solver, cfg, host, box, buf, merit, n_iters=None):
+    """What helpers.check_solve_outputs checks, for the opt-in forms (merit: a run whose `cost` is the
+    merit J): status set and iteration counts, the lamb history, U inside the input box, X the
+    oracle's rollout of U (to ROLLOUT_TOL), `cost` = rollout cost (+ penalty(X, U) with the barrier
+    cost) and at most that of the caller's inputs (to ROLLOUT_TOL's cost tolerance: a step is accepted
+    only if it lowers it)."""
+    import torch
+    from oracle import oracle as orc
+    f64 = solver.dtype == torch.float64
+    npdt = np.float64 if f64 else np.float32
+    x_tol, c_tol = ROLLOUT_TOL["f64" if f64 else "f32"]
+    st, it = buf["status"].cpu().numpy(), buf["iters"].cpu().numpy()
+    lamb, J = buf["lamb"].double().cpu().numpy(), buf["cost"].double().cpu().numpy()
+    assert np.isfinite(J).all()
+    if n_iters is None:
+        assert np.isin(st, [1, 2, 3]).all() and it.min() >= 1 and it.max() <= cfg.max_iter
+        assert (it[st == 2] == cfg.max_iter).all() and (lamb[st == 3] > cfg.max_lamb).all()
+    else:
+        assert np.isin(st, [0, 1, 3]).all() and (it == n_iters).all()
+    j = np.log(lamb / np.asarray(host["lamb"], dtype=npdt)) / np.log(cfg.lamb_factor)
+    assert np.abs(j - np.rint(j)).max() * np.log(cfg.lamb_factor) <= (1e-9 if f64 else 1e-5)
+    assert (np.abs(np.rint(j)) <= it).all() and ((np.rint(j).astype(np.int64) - it) % 2 == 0).all()
+    X, U, x_term = (to_host(solver, buf[key]) for key in ("X", "U", "x_term"))
+    assert np.array_equal(X[:, :, 0], np.asarray(host["X"][:, :, 0], dtype=npdt))
+    u_max = np.asarray(list(cfg.u_max)[:cfg.m], dtype=npdt)
+    assert (np.abs(U) <= u_max[None, :, None]).all()
+    Xr, Ur, cr = orc.rollout_batch(cfg, X, U, x_term)
+    assert batch_rel_err(X, Xr) <= x_tol
+    Jr = cr + (penalty(cfg, Xr, Ur, host["obs"], box) if merit else 0.0)
+    assert (np.abs(J - Jr) / np.maximum(np.abs(Jr), 1.0)).max() <= c_tol
+    X0, U0, c0 = orc.rollout_batch(cfg, np.asarray(host["X"], dtype=npdt),
+                                   np.asarray(host["U"], dtype=npdt), x_term)
+    J0 = c0 + (penalty(cfg, X0, U0, host["obs"], box) if merit else 0.0)
+    assert ((J - J0) / np.maximum(np.abs(J0), 1.0)).max() <= c_tol
+
+
+@functools.lru_cache(maxsize=None)
+def long_horizon_bound():
+    """The bounds on (X, U) for b4_N64 with its box, 3 iterations (no lane kernel has a recorded error
+    at that horizon): ten times k_lane_iterate_model's own batch_rel_err against reference(merit=False)
+    on the same batch and count, or TOL_SOLVE if that is larger.  One run on the device, shared."""
+    cfg, host, box = make_case("b4_N64", box=True)
+    soft_ref = lane_reference("b4_N64", 1, 3)
+    soft = lane_solver(cfg, host, box)
+    assert soft.iterate_kernel(9) == LANE_BOX_NAME
+    buf = run(soft, host, 3)
+    same = buf["lamb"].cpu().numpy() == soft_ref["lamb"]
+    assert same.mean() >= 0.97
+    base = (batch_rel_err(to_host(soft, buf["X"])[same], soft_ref["X"][same]),
+            batch_rel_err(to_host(soft, buf["U"])[same], soft_ref["U"][same]))
+    print(f"b4_N64: model kernel X {base[0]:.3e} U {base[1]:.3e}")
+    return tuple(max(10.0 * err, TOL_SOLVE) for err in base)

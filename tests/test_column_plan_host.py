@@ -16,32 +16,13 @@ wavefront, X refused.
 Workspace: i2lqr_workspace_bytes and the choice read ONE range predicate.  What the launcher always
 did and still does: with "group_workspace" 0 a size is reported in the automatic range although the
 form is never chosen (asserted as it is)."""
-import shutil
-import subprocess
 from pathlib import Path
 
-import pytest
+from helpers import HOST_CHECK_PRELUDE, run_host_program
 
 CSRC = Path(__file__).resolve().parent.parent / "ilqr_iterative_tasks_amd" / "csrc"
 
-PROGRAM = r"""
-#include "i2lqr_column_plan.hpp"
-
-#include <cstdio>
-#include <cstring>
-#include <initializer_list>
-
-using namespace i2lqr;
-
-static int bad = 0;
-#define CHECK(cond)                                              \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      if (bad < 40) std::printf("FAILED line %d: %s\n", __LINE__, #cond); \
-      bad++;                                                     \
-    }                                                            \
-  } while (0)
-
+PROGRAM = '#include "i2lqr_column_plan.hpp"\n' + HOST_CHECK_PRELUDE + r"""
 static ColumnFit bicycle(bool f64, int n, int N, size_t wave, size_t fstep, size_t g8, size_t g16,
                          size_t gws, int64_t ws, size_t s8x2, size_t s8x3, size_t s16x2, size_t s16x3) {
   ColumnFit f;
@@ -484,16 +465,4 @@ int main() {
 
 
 def test_column_plan_rules_against_literals(tmp_path):
-    cxx = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    src = tmp_path / "column_plan_check.cpp"
-    src.write_text(PROGRAM)
-    exe = tmp_path / "column_plan_check"
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
-                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    print(run.stdout, run.stderr)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "0 failed" in run.stdout
+    run_host_program(tmp_path, "column_plan_check", PROGRAM, [CSRC])

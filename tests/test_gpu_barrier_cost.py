@@ -15,10 +15,10 @@ import functools
 import numpy as np
 import pytest
 
-from helpers import ROLLOUT_TOL, TOL_SOLVE, batch_rel_err, dev_batch, to_host
+from helpers import TOL_SOLVE, batch_rel_err, dev_batch, to_host
 from opt_in_cases import MARGIN, MAX_LEFT_OUT, MERIT_RUNS, MERIT_TERMINATION_RUNS, make_case
-from opt_in_gpu import BOX_NAME, MERIT_NAME, make_solver, options_for, run, same_bits
-from opt_in_reference import SPEED_LIMIT, Box, controlled_laps, penalty, reference, top_speeds
+from opt_in_gpu import BOX_NAME, MERIT_NAME, check_outputs, make_solver, options_for, run, same_bits
+from opt_in_reference import SPEED_LIMIT, Box, controlled_laps, reference, top_speeds
 
 pytestmark = pytest.mark.gpu
 
@@ -85,47 +85,12 @@ def test_two_iterations_at_a_horizon_of_one_match_the_reference(torch_mod, case,
                          ids=[f"{c}-A{A}" for c, _, A in MERIT_TERMINATION_RUNS])
 def test_solve_to_termination_matches_the_reference(torch_mod, case, n_iters, A):
     solver, cfg, host, box, buf = _check_run(case, None, A)
-    _check_merit_outputs(solver, cfg, host, box, buf)
+    check_outputs(solver, cfg, host, box, buf, True)
     # the device's figures beside the CPU's (README): LAMB_OVERFLOW exits and the mean final J
     ref = _reference(case, None, A)
     st, J = buf["status"].cpu().numpy(), buf["cost"].cpu().numpy()
     print(f"{case}: LAMB_OVERFLOW exits {(st == 3).sum()} (reference {(ref['status'] == 3).sum()}), "
           f"mean final J {J.mean():.6g} (reference {ref['cost'].mean():.6g})")
-
-
-def _check_merit_outputs(solver, cfg, host, box, buf, n_iters=None):
-    """What helpers.check_solve_outputs checks, for a run whose `cost` is the merit: status set and
-    iteration counts, the lamb history, U inside the input box, X the oracle's rollout of U (to
-    ROLLOUT_TOL), J = rollout cost + penalty(X, U) and J at most the J of the caller's inputs (to
-    ROLLOUT_TOL's cost tolerance: a step is accepted only if it lowers J)."""
-    import torch
-    from oracle import oracle as orc
-    f64 = solver.dtype == torch.float64
-    npdt = np.float64 if f64 else np.float32
-    x_tol, c_tol = ROLLOUT_TOL["f64" if f64 else "f32"]
-    st, it = buf["status"].cpu().numpy(), buf["iters"].cpu().numpy()
-    lamb, J = buf["lamb"].double().cpu().numpy(), buf["cost"].double().cpu().numpy()
-    assert np.isfinite(J).all()
-    if n_iters is None:
-        assert np.isin(st, [1, 2, 3]).all() and it.min() >= 1 and it.max() <= cfg.max_iter
-        assert (it[st == 2] == cfg.max_iter).all() and (lamb[st == 3] > cfg.max_lamb).all()
-    else:
-        assert np.isin(st, [0, 1, 3]).all() and (it == n_iters).all()
-    j = np.log(lamb / np.asarray(host["lamb"], dtype=npdt)) / np.log(cfg.lamb_factor)
-    assert np.abs(j - np.rint(j)).max() * np.log(cfg.lamb_factor) <= (1e-9 if f64 else 1e-5)
-    assert (np.abs(np.rint(j)) <= it).all() and ((np.rint(j).astype(np.int64) - it) % 2 == 0).all()
-    X, U, x_term = (to_host(solver, buf[key]) for key in ("X", "U", "x_term"))
-    assert np.array_equal(X[:, :, 0], np.asarray(host["X"][:, :, 0], dtype=npdt))
-    u_max = np.asarray(list(cfg.u_max)[:cfg.m], dtype=npdt)
-    assert (np.abs(U) <= u_max[None, :, None]).all()
-    Xr, Ur, cr = orc.rollout_batch(cfg, X, U, x_term)
-    assert batch_rel_err(X, Xr) <= x_tol
-    Jr = cr + penalty(cfg, Xr, Ur, host["obs"], box)
-    assert (np.abs(J - Jr) / np.maximum(np.abs(Jr), 1.0)).max() <= c_tol
-    X0, U0, c0 = orc.rollout_batch(cfg, np.asarray(host["X"], dtype=npdt),
-                                   np.asarray(host["U"], dtype=npdt), x_term)
-    J0 = c0 + penalty(cfg, X0, U0, host["obs"], box)
-    assert ((J - J0) / np.maximum(np.abs(J0), 1.0)).max() <= c_tol
 
 
 def test_off_is_off(torch_mod):
@@ -177,8 +142,8 @@ def test_fp32_outputs_are_consistent(torch_mod):
     box = Box(cfg.n, {2: (0.0, 10.0)})
     solver = _solver(cfg, box)
     assert solver.iterate_kernel(67) == MERIT_NAME
-    _check_merit_outputs(solver, cfg, host, box, run(solver, host, 3), n_iters=3)
-    _check_merit_outputs(solver, cfg, host, box, run(solver, host, None))
+    check_outputs(solver, cfg, host, box, run(solver, host, 3), True, n_iters=3)
+    check_outputs(solver, cfg, host, box, run(solver, host, None), True)
 
 
 def test_refusals_name_the_option(torch_mod):

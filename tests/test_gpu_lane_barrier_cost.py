@@ -1,7 +1,7 @@
 """GPU tests of "lane_barrier_cost" (include/i2lqr.h): k_lane_iterate_merit through the C-ABI - the
 accept / reject step and the convergence test of the one-problem-per-lane kernel see the merit
 J = c + P, `cost` returns J - batch-minor and batch-tiled, against
-opt_in_reference.reference(merit=True) on the runs of lane_merit_cases.py.
+opt_in_reference.reference(merit=True) on the barrier-cost runs of lane_cases.py.
 
 Tolerances (fp64) and the conditioning rule are test_gpu_barrier_cost.py's: identical lamb, iters and
 status, X (U for fixed counts) to TOL_SOLVE, `cost` as J to 1e-8 relative, gains to 1e-7, on the
@@ -13,20 +13,24 @@ keep the bits: against the kernel's own runs, bit for bit (the far box: as numbe
 The N = 64 set: no lane kernel has a recorded error at that horizon, so the bound on X and U is
 taken in the test: ten times k_lane_iterate_model's own batch_rel_err against
 reference(merit=False) on the same batch and count, or TOL_SOLVE if that is larger."""
+import functools
+
 import numpy as np
 import pytest
 
-from helpers import ROLLOUT_TOL, TOL_SOLVE, batch_rel_err, dev_batch, to_host
-from lane_merit_cases import (IDS, LANE_MERIT_RUNS, lane_merit_reference)
+from helpers import TOL_SOLVE, batch_rel_err, dev_batch, to_host
+from lane_cases import LANE_MERIT_IDS, LANE_MERIT_RUNS, lane_reference
 from opt_in_cases import MARGIN, MAX_LEFT_OUT, SEED, make_case, on_layout
-from opt_in_gpu import OUTPUTS, make_solver, run, same_bits
-from opt_in_reference import Box, penalty, reference
+from opt_in_gpu import LANE_BOX_NAME as BOX_NAME
+from opt_in_gpu import LANE_MERIT_NAME as MERIT_NAME
+from opt_in_gpu import LANE_OBS_NAME as OBS_NAME
+from opt_in_gpu import (OUTPUTS, check_outputs, checked_lane_solver, lane_solver, long_horizon_bound,
+                        records, run, same_bits)
+from opt_in_reference import Box, reference
 
 pytestmark = pytest.mark.gpu
 
-MERIT_NAME = "k_lane_iterate (barrier cost)"
-BOX_NAME = "k_lane_iterate (state box)"
-OBS_NAME = "k_lane_iterate (several obstacles)"
+_merit_solver = functools.partial(checked_lane_solver, merit=True)  # (cfg, host, box, layout, **options)
 
 
 @pytest.fixture(scope="module")
@@ -36,69 +40,11 @@ def torch_mod():
     return torch
 
 
-def _records(host):
-    return host["obs"].shape[1] if host["obs"] is not None and host["obs"].ndim == 3 else None
-
-
-def _lane(cfg, host=None, box=None, layout=1, merit=True, models=True, **options):
-    """A solver of cfg on a lane layout: the scheduling options, "lane_models", "obstacles" for the
-    records of `host`, "lane_barrier_cost", then the box."""
-    if models:
-        options["lane_models"] = 1
-    if host is not None and _records(host):
-        options["obstacles"] = _records(host)
-    if merit:
-        options["lane_barrier_cost"] = 1
-    return make_solver(on_layout(cfg, layout), box, **options)
-
-
-def _merit_solver(cfg, host, box=None, layout=1, **options):
-    solver = _lane(cfg, host, box, layout, **options)
-    B = host["X"].shape[0]
-    assert solver.iterate_kernel(B) == solver.solve_kernel(B) == MERIT_NAME
-    return solver
-
-
-def _check_merit_outputs(solver, cfg, host, box, buf, n_iters=None):
-    """test_gpu_barrier_cost.py's check of a run whose `cost` is the merit: status set and iteration
-    counts, the lamb history, U inside the input box, X the oracle's rollout of U (to ROLLOUT_TOL),
-    J = rollout cost + penalty(X, U) and J at most the J of the caller's inputs (to ROLLOUT_TOL's
-    cost tolerance: a step is accepted only if it lowers J)."""
-    import torch
-    from oracle import oracle as orc
-    f64 = solver.dtype == torch.float64
-    npdt = np.float64 if f64 else np.float32
-    x_tol, c_tol = ROLLOUT_TOL["f64" if f64 else "f32"]
-    st, it = buf["status"].cpu().numpy(), buf["iters"].cpu().numpy()
-    lamb, J = buf["lamb"].double().cpu().numpy(), buf["cost"].double().cpu().numpy()
-    assert np.isfinite(J).all()
-    if n_iters is None:
-        assert np.isin(st, [1, 2, 3]).all() and it.min() >= 1 and it.max() <= cfg.max_iter
-        assert (it[st == 2] == cfg.max_iter).all() and (lamb[st == 3] > cfg.max_lamb).all()
-    else:
-        assert np.isin(st, [0, 1, 3]).all() and (it == n_iters).all()
-    j = np.log(lamb / np.asarray(host["lamb"], dtype=npdt)) / np.log(cfg.lamb_factor)
-    assert np.abs(j - np.rint(j)).max() * np.log(cfg.lamb_factor) <= (1e-9 if f64 else 1e-5)
-    assert (np.abs(np.rint(j)) <= it).all() and ((np.rint(j).astype(np.int64) - it) % 2 == 0).all()
-    X, U, x_term = (to_host(solver, buf[key]) for key in ("X", "U", "x_term"))
-    assert np.array_equal(X[:, :, 0], np.asarray(host["X"][:, :, 0], dtype=npdt))
-    u_max = np.asarray(list(cfg.u_max)[:cfg.m], dtype=npdt)
-    assert (np.abs(U) <= u_max[None, :, None]).all()
-    Xr, Ur, cr = orc.rollout_batch(cfg, X, U, x_term)
-    assert batch_rel_err(X, Xr) <= x_tol
-    Jr = cr + penalty(cfg, Xr, Ur, host["obs"], box)
-    assert (np.abs(J - Jr) / np.maximum(np.abs(Jr), 1.0)).max() <= c_tol
-    X0, U0, c0 = orc.rollout_batch(cfg, np.asarray(host["X"], dtype=npdt),
-                                   np.asarray(host["U"], dtype=npdt), x_term)
-    J0 = c0 + penalty(cfg, X0, U0, host["obs"], box)
-    assert ((J - J0) / np.maximum(np.abs(J0), 1.0)).max() <= c_tol
-
-
-@pytest.mark.parametrize("case,n_iters,layout", LANE_MERIT_RUNS, ids=IDS)
+@pytest.mark.parametrize("case,n_iters,layout", LANE_MERIT_RUNS, ids=LANE_MERIT_IDS)
 def test_table_runs_match_the_reference(torch_mod, case, n_iters, layout):
     cfg, host, box = make_case(case, box=True, layout=layout)
     B = host["X"].shape[0]
-    ref = lane_merit_reference(case, n_iters, layout)
+    ref = lane_reference(case, 1, n_iters, layout, merit=True)
     keep = ref["margin"] >= MARGIN
     print(f"{case}: {keep.sum()} of {B} problems compared, smallest margin {ref['margin'].min():.3g}")
     assert (~keep).mean() <= MAX_LEFT_OUT[n_iters is None]
@@ -117,7 +63,7 @@ def test_table_runs_match_the_reference(torch_mod, case, n_iters, layout):
         assert batch_rel_err(to_host(solver, buf["K"])[keep], ref["K"][keep]) < 1e-7
         assert batch_rel_err(to_host(solver, buf["k"])[keep], ref["k"][keep], floor=1.0) < 1e-7
     else:
-        _check_merit_outputs(solver, cfg, host, box, buf)
+        check_outputs(solver, cfg, host, box, buf, True)
         print(f"{case}: LAMB_OVERFLOW exits {(got['status'] == 3).sum()} "
               f"(reference {(ref['status'] == 3).sum()})")
 
@@ -128,15 +74,8 @@ def test_long_horizon_error_is_the_model_kernels(torch_mod):
     batch and count (the penalty adds nothing to what X and U are computed from), or TOL_SOLVE if
     that is larger."""
     cfg, host, box = make_case("b4_N64", box=True)
-    soft_ref = lane_merit_reference("b4_N64", 3, merit=False)
-    soft = _lane(cfg, host, box, merit=False)
-    assert soft.iterate_kernel(9) == BOX_NAME
-    buf = run(soft, host, 3)
-    same = buf["lamb"].cpu().numpy() == soft_ref["lamb"]
-    assert same.mean() >= 0.97
-    base = (batch_rel_err(to_host(soft, buf["X"])[same], soft_ref["X"][same]),
-            batch_rel_err(to_host(soft, buf["U"])[same], soft_ref["U"][same]))
-    ref = lane_merit_reference("b4_N64", 3)
+    bound = long_horizon_bound()  # (prints the model kernel's own error)
+    ref = lane_reference("b4_N64", 1, 3, merit=True)
     assert ref["margin"].min() >= MARGIN
     solver = _merit_solver(cfg, host, box)
     buf = run(solver, host, 3)
@@ -144,10 +83,9 @@ def test_long_horizon_error_is_the_model_kernels(torch_mod):
         assert np.array_equal(buf[key].cpu().numpy(), ref[key]), key
     got = (batch_rel_err(to_host(solver, buf["X"]), ref["X"]),
            batch_rel_err(to_host(solver, buf["U"]), ref["U"]))
-    print(f"b4_N64: model kernel X {base[0]:.3e} U {base[1]:.3e}; "
-          f"barrier-cost kernel X {got[0]:.3e} U {got[1]:.3e}")
-    for mine, model_err in zip(got, base):
-        assert mine <= max(10.0 * model_err, TOL_SOLVE)
+    print(f"b4_N64: barrier-cost kernel X {got[0]:.3e} U {got[1]:.3e}")
+    for mine, most in zip(got, bound):
+        assert mine <= most
     np.testing.assert_allclose(buf["cost"].cpu().numpy(), ref["cost"], rtol=1e-8)
 
 
@@ -156,7 +94,7 @@ def test_off_is_off(torch_mod):
     without a box and records, the plain lane kernels'."""
     cfg, host, box = make_case("b6", box=True)
     B = host["X"].shape[0]
-    boxed = _lane(cfg, host, box, merit=False)
+    boxed = lane_solver(cfg, host, box)
     assert boxed.iterate_kernel(B) == boxed.solve_kernel(B) == BOX_NAME
     want = {n: run(boxed, host, n) for n in (3, None)}
     solver = _merit_solver(cfg, host, box)
@@ -168,7 +106,7 @@ def test_off_is_off(torch_mod):
         assert solver.iterate_kernel(B) == solver.solve_kernel(B) == name
     for n in (3, None):
         same_bits(torch_mod, run(solver, host, n), want[n])
-    plain = _lane(cfg, merit=False, models=False)
+    plain = lane_solver(cfg, models=False)
     names = plain.iterate_kernel(B), plain.solve_kernel(B)
     assert not any("(" in name for name in names)
     want = {n: run(plain, host, n) for n in (3, None)}
@@ -228,7 +166,7 @@ def test_a_far_box_is_no_box(torch_mod, case):
         for n in (3, None):
             want, got = run(base, batch, n), run(boxed, batch, n)
             for key in OUTPUTS:
-                assert torch_mod.equal(got[key], want[key]), (key, n, _records(batch))
+                assert torch_mod.equal(got[key], want[key]), (key, n, records(batch))
 
 
 @pytest.mark.parametrize("K", [3, 8])
@@ -257,8 +195,8 @@ def test_fp32_outputs_are_consistent(torch_mod, layout):
     else:
         cfg, host, box = make_case("b6_T128_K3", box=True, dtype="f32", layout=2)
     solver = _merit_solver(cfg, host, box, layout)
-    _check_merit_outputs(solver, cfg, host, box, run(solver, host, 3), n_iters=3)
-    _check_merit_outputs(solver, cfg, host, box, run(solver, host, None))
+    check_outputs(solver, cfg, host, box, run(solver, host, 3), True, n_iters=3)
+    check_outputs(solver, cfg, host, box, run(solver, host, None), True)
 
 
 def test_solve_stays_a_single_launch(torch_mod):
@@ -272,7 +210,7 @@ def test_solve_stays_a_single_launch(torch_mod):
     box = Box(cfg.n, {2: (0.0, 10.0)})
     solver = _merit_solver(cfg, host, box)
     want = run(solver, host, None)
-    _check_merit_outputs(solver, cfg, host, box, want)
+    check_outputs(solver, cfg, host, box, want, True)
     solver.set_compaction(64)
     assert solver.solve_kernel(4160) == MERIT_NAME
     same_bits(torch_mod, run(solver, host, None), want)
@@ -285,7 +223,7 @@ def test_names_and_refusals(torch_mod):
     cfg, host, box = make_case("b6_K2", box=True)
     B = host["X"].shape[0]
     # the name ranks above the several obstacles' and the state box's
-    solver = _lane(cfg, host, merit=False)
+    solver = lane_solver(cfg, host)
     assert solver.iterate_kernel(B) == OBS_NAME
     solver.set_option("lane_barrier_cost", 1)
     assert solver.iterate_kernel(B) == solver.solve_kernel(B) == MERIT_NAME

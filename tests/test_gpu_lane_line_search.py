@@ -1,7 +1,7 @@
 """GPU tests of "lane_line_search" (include/i2lqr.h): k_lane_iterate_ls through the C-ABI - 2, 4 or 8
 step sizes per iteration on the one-problem-per-lane kernel, with the soft accept test or the barrier
-cost, batch-minor and batch-tiled - against opt_in_reference.reference(A, merit=...) on the runs of
-lane_ls_cases.py.
+cost, batch-minor and batch-tiled - against opt_in_reference.reference(A, merit=...) on the line-search
+runs of lane_cases.py.
 
 Tolerances (fp64) and the conditioning rule are test_gpu_lane_barrier_cost.py's: identical lamb,
 iters and status, X (U for fixed counts) to TOL_SOLVE, `cost` to 1e-8 relative, gains to 1e-7, on the
@@ -17,18 +17,18 @@ or TOL_SOLVE if that is larger."""
 import numpy as np
 import pytest
 
-from helpers import ROLLOUT_TOL, TOL_SOLVE, batch_rel_err, dev_batch, to_host
-from lane_ls_cases import FULL_STEP_RUNS, IDS, LANE_LS_RUNS, lane_ls_reference, make_ls_case, run_id
+from helpers import TOL_SOLVE, batch_rel_err, dev_batch, to_host
+from lane_cases import FULL_STEP_RUNS, LANE_LS_RUNS, lane_reference, ls_run_ids, make_lane_case
 from opt_in_cases import MARGIN, MAX_LEFT_OUT, SEED, make_case, on_layout
-from opt_in_gpu import make_solver, run, same_bits
-from opt_in_reference import Box, penalty
+from opt_in_gpu import LANE_BOX_NAME as BOX_NAME
+from opt_in_gpu import LANE_LS_NAME as LS_NAME
+from opt_in_gpu import LANE_MERIT_NAME as MERIT_NAME
+from opt_in_gpu import LANE_OBS_NAME as OBS_NAME
+from opt_in_gpu import (check_outputs, checked_lane_solver, lane_name, lane_solver, long_horizon_bound,
+                        make_solver, run, same_bits)
+from opt_in_reference import Box
 
 pytestmark = pytest.mark.gpu
-
-LS_NAME = "k_lane_iterate (line search)"
-MERIT_NAME = "k_lane_iterate (barrier cost)"
-BOX_NAME = "k_lane_iterate (state box)"
-OBS_NAME = "k_lane_iterate (several obstacles)"
 
 
 @pytest.fixture(scope="module")
@@ -38,102 +38,18 @@ def torch_mod():
     return torch
 
 
-def _records(host):
-    return host["obs"].shape[1] if host["obs"] is not None and host["obs"].ndim == 3 else None
-
-
-def _lane(cfg, host=None, box=None, layout=1, A=4, merit=False, **options):
-    """A solver of cfg on a lane layout: the scheduling options, "lane_models", "obstacles" for the
-    records of `host`, "lane_barrier_cost", "lane_line_search" (A > 1), then the box."""
-    options["lane_models"] = 1
-    if host is not None and _records(host):
-        options["obstacles"] = _records(host)
-    if merit:
-        options["lane_barrier_cost"] = 1
-    if A > 1:
-        options["lane_line_search"] = A
-    return make_solver(on_layout(cfg, layout), box, **options)
-
-
-def _name(host, box, merit):
-    """names_model's precedence: barrier cost > box > obstacles > line search."""
-    if merit:
-        return MERIT_NAME
-    if box is not None and box.active:
-        return BOX_NAME
-    return OBS_NAME if _records(host) else LS_NAME
-
-
-def _ls_solver(cfg, host, box=None, layout=1, A=4, merit=False, **options):
-    solver = _lane(cfg, host, box, layout, A, merit, **options)
-    B = host["X"].shape[0]
-    assert solver.iterate_kernel(B) == solver.solve_kernel(B) == _name(host, box, merit)
-    return solver
-
-
-def _check_outputs(solver, cfg, host, box, buf, merit, n_iters=None):
-    """test_gpu_lane_barrier_cost.py's _check_merit_outputs, for soft runs without the penalty: status
-    set and iteration counts, the lamb history, U inside the input box, X the oracle's rollout of U
-    (to ROLLOUT_TOL), `cost` = rollout cost (+ penalty(X, U) with the barrier cost) and at most that
-    of the caller's inputs."""
-    import torch
-    from oracle import oracle as orc
-    f64 = solver.dtype == torch.float64
-    npdt = np.float64 if f64 else np.float32
-    x_tol, c_tol = ROLLOUT_TOL["f64" if f64 else "f32"]
-    st, it = buf["status"].cpu().numpy(), buf["iters"].cpu().numpy()
-    lamb, J = buf["lamb"].double().cpu().numpy(), buf["cost"].double().cpu().numpy()
-    assert np.isfinite(J).all()
-    if n_iters is None:
-        assert np.isin(st, [1, 2, 3]).all() and it.min() >= 1 and it.max() <= cfg.max_iter
-        assert (it[st == 2] == cfg.max_iter).all() and (lamb[st == 3] > cfg.max_lamb).all()
-    else:
-        assert np.isin(st, [0, 1, 3]).all() and (it == n_iters).all()
-    j = np.log(lamb / np.asarray(host["lamb"], dtype=npdt)) / np.log(cfg.lamb_factor)
-    assert np.abs(j - np.rint(j)).max() * np.log(cfg.lamb_factor) <= (1e-9 if f64 else 1e-5)
-    assert (np.abs(np.rint(j)) <= it).all() and ((np.rint(j).astype(np.int64) - it) % 2 == 0).all()
-    X, U, x_term = (to_host(solver, buf[key]) for key in ("X", "U", "x_term"))
-    assert np.array_equal(X[:, :, 0], np.asarray(host["X"][:, :, 0], dtype=npdt))
-    u_max = np.asarray(list(cfg.u_max)[:cfg.m], dtype=npdt)
-    assert (np.abs(U) <= u_max[None, :, None]).all()
-    Xr, Ur, cr = orc.rollout_batch(cfg, X, U, x_term)
-    assert batch_rel_err(X, Xr) <= x_tol
-    Jr = cr + (penalty(cfg, Xr, Ur, host["obs"], box) if merit else 0.0)
-    assert (np.abs(J - Jr) / np.maximum(np.abs(Jr), 1.0)).max() <= c_tol
-    X0, U0, c0 = orc.rollout_batch(cfg, np.asarray(host["X"], dtype=npdt),
-                                   np.asarray(host["U"], dtype=npdt), x_term)
-    J0 = c0 + (penalty(cfg, X0, U0, host["obs"], box) if merit else 0.0)
-    assert ((J - J0) / np.maximum(np.abs(J0), 1.0)).max() <= c_tol
-
-
-@pytest.fixture(scope="module")
-def long_horizon_bound(torch_mod):
-    """test_long_horizon_error_is_the_model_kernels' bound for b4_N64, 3 iterations: (X, U)."""
-    cfg, host, box = make_case("b4_N64", box=True)
-    soft_ref = lane_ls_reference("b4_N64", 1, 3)
-    soft = _lane(cfg, host, box, A=1)
-    assert soft.iterate_kernel(9) == BOX_NAME
-    buf = run(soft, host, 3)
-    same = buf["lamb"].cpu().numpy() == soft_ref["lamb"]
-    assert same.mean() >= 0.97
-    base = (batch_rel_err(to_host(soft, buf["X"])[same], soft_ref["X"][same]),
-            batch_rel_err(to_host(soft, buf["U"])[same], soft_ref["U"][same]))
-    print(f"b4_N64: model kernel X {base[0]:.3e} U {base[1]:.3e}")
-    return tuple(max(10.0 * err, TOL_SOLVE) for err in base)
-
-
-@pytest.mark.parametrize("case,A,n_iters,layout,merit", LANE_LS_RUNS, ids=IDS)
-def test_table_runs_match_the_reference(torch_mod, long_horizon_bound, case, A, n_iters, layout, merit):
-    """The rows of lane_ls_cases.py, the weighted bicycle6 sets among them: the instantiations whose
+@pytest.mark.parametrize("case,A,n_iters,layout,merit", LANE_LS_RUNS, ids=ls_run_ids(LANE_LS_RUNS))
+def test_table_runs_match_the_reference(torch_mod, case, A, n_iters, layout, merit):
+    """The line-search rows of lane_cases.py, the weighted bicycle6 sets among them: the instantiations whose
     trial passes hold two candidates (A = 4: two passes, A = 8: four)."""
-    cfg, host, box = make_ls_case(case, layout)
+    cfg, host, box = make_lane_case(case, layout)
     B = host["X"].shape[0]
-    ref = lane_ls_reference(case, A, n_iters, layout, merit)
+    ref = lane_reference(case, A, n_iters, layout, merit)
     keep = ref["margin"] >= MARGIN
     print(f"{case}: {keep.sum()} of {B} problems compared, smallest margin {ref['margin'].min():.3g}, "
           f"short steps in {(ref['jstar'] > 0).any(axis=0).mean():.2f} of the problems")
     assert (~keep).mean() <= MAX_LEFT_OUT[n_iters is None]
-    solver = _ls_solver(cfg, host, box, layout, A, merit)
+    solver = checked_lane_solver(cfg, host, box, layout, A, merit)
     buf = run(solver, host, n_iters)
     got = {key: buf[key].cpu().numpy() for key in ("lamb", "iters", "status", "cost")}
     same = (got["lamb"] == ref["lamb"]) & (got["iters"] == ref["iters"]) & \
@@ -141,7 +57,7 @@ def test_table_runs_match_the_reference(torch_mod, long_horizon_bound, case, A, 
     print(f"{case}: reference's lamb, iters and status on {same[keep].sum()} of {keep.sum()} compared "
           f"problems ({same.sum()} of {B} overall)")
     assert same[keep].all(), f"problems {np.flatnonzero(keep & ~same)} took another branch"
-    x_tol, u_tol = long_horizon_bound if case == "b4_N64" else (TOL_SOLVE, TOL_SOLVE)
+    x_tol, u_tol = long_horizon_bound() if case == "b4_N64" else (TOL_SOLVE, TOL_SOLVE)
     x_err = batch_rel_err(to_host(solver, buf["X"])[keep], ref["X"][keep])
     print(f"{case}: X {x_err:.3e}")
     assert x_err <= x_tol if case == "b4_N64" else x_err < x_tol
@@ -153,21 +69,20 @@ def test_table_runs_match_the_reference(torch_mod, long_horizon_bound, case, A, 
         assert batch_rel_err(to_host(solver, buf["K"])[keep], ref["K"][keep]) < 1e-7
         assert batch_rel_err(to_host(solver, buf["k"])[keep], ref["k"][keep], floor=1.0) < 1e-7
     else:
-        _check_outputs(solver, cfg, host, box, buf, merit)
+        check_outputs(solver, cfg, host, box, buf, merit)
         print(f"{case}: LAMB_OVERFLOW exits {(got['status'] == 3).sum()} "
               f"(reference {(ref['status'] == 3).sum()})")
 
 
-@pytest.mark.parametrize("case,A,n_iters,layout,merit", FULL_STEP_RUNS,
-                         ids=[run_id(*r) for r in FULL_STEP_RUNS])
+@pytest.mark.parametrize("case,A,n_iters,layout,merit", FULL_STEP_RUNS, ids=ls_run_ids(FULL_STEP_RUNS))
 def test_a_run_without_short_steps_is_the_one_step_kernels(torch_mod, case, A, n_iters, layout, merit):
     """Horizon 1 with the barrier cost: the reference takes the full step in every iteration of every
     problem, and candidate 0 is computed with k_lane_iterate_merit's arithmetic."""
     cfg, host, box = make_case(case, box=True, layout=layout)
-    ref = lane_ls_reference(case, A, n_iters, layout, merit)
+    ref = lane_reference(case, A, n_iters, layout, merit)
     assert (ref["jstar"] == 0).all()
-    want = run(_lane(cfg, host, box, layout, A=1, merit=merit), host, n_iters)
-    same_bits(torch_mod, run(_ls_solver(cfg, host, box, layout, A, merit), host, n_iters), want)
+    want = run(lane_solver(cfg, host, box, layout, merit=merit), host, n_iters)
+    same_bits(torch_mod, run(checked_lane_solver(cfg, host, box, layout, A, merit), host, n_iters), want)
 
 
 @pytest.mark.parametrize("merit", [False, True], ids=["soft", "merit"])
@@ -176,11 +91,11 @@ def test_off_is_off(torch_mod, merit):
     records, the plain lane kernels'."""
     cfg, host, box = make_case("b6", box=True)
     B = host["X"].shape[0]
-    base = _lane(cfg, host, box, A=1, merit=merit)
+    base = lane_solver(cfg, host, box, merit=merit)
     name = MERIT_NAME if merit else BOX_NAME
     assert base.iterate_kernel(B) == base.solve_kernel(B) == name
     want = {n: run(base, host, n) for n in (3, None)}
-    solver = _ls_solver(cfg, host, box, A=4, merit=merit)
+    solver = checked_lane_solver(cfg, host, box, A=4, merit=merit)
     on = run(solver, host, 3)
     assert not torch_mod.equal(on["X"], want[3]["X"])  # (short steps are taken on this set)
     # (the names do not tell: with a box or the barrier cost they are the same on and off)
@@ -198,7 +113,7 @@ def test_off_is_off(torch_mod, merit):
     names = plain.iterate_kernel(B), plain.solve_kernel(B)
     assert not any("(" in name for name in names)
     want = {n: run(plain, host, n) for n in (3, None)}
-    solver = _ls_solver(cfg, host, A=4)  # one record, no box, no barrier cost: a valid model
+    solver = checked_lane_solver(cfg, host, A=4)  # one record, no box, no barrier cost: a valid model
     assert solver.iterate_kernel(B) == LS_NAME
     assert not torch_mod.equal(run(solver, host, 3)["X"], want[3]["X"])
     solver.set_option("lane_line_search", 0)
@@ -219,9 +134,9 @@ def test_scheduling_options_keep_the_bits(torch_mod, K):
     variants += [dict(merge_inputs=1), dict(lds_gain_steps=0), dict(stagger=2),
                  dict(helper_wavefront=1, checkpoint_states=1, state_buffers=1)]
     for n in (3, None):
-        want = run(_ls_solver(cfg, host, box, merit=True), host, n)
+        want = run(checked_lane_solver(cfg, host, box, A=4, merit=True), host, n)
         for options in variants:
-            got = run(_ls_solver(cfg, host, box, merit=True, **options), host, n)
+            got = run(checked_lane_solver(cfg, host, box, A=4, merit=True, **options), host, n)
             same_bits(torch_mod, got, want, options)
 
 
@@ -231,11 +146,11 @@ def test_eight_step_sizes_in_two_rounds(torch_mod, merit):
     set, and on exactly those problems the kernel's run is the reference's - the second pass's
     candidates reach the argmin and the winner's pass."""
     cfg, host, box = make_case("b6_K2", box=True)
-    ref = lane_ls_reference("b6_K2", 8, 3, 1, merit)
+    ref = lane_reference("b6_K2", 8, 3, 1, merit)
     far = (ref["jstar"] >= 4).any(axis=0) & (ref["margin"] >= MARGIN)
     print(f"b6_K2: {far.sum()} problems take a step with j >= 4")
     assert far.any()
-    solver = _ls_solver(cfg, host, box, A=8, merit=merit)
+    solver = checked_lane_solver(cfg, host, box, A=8, merit=merit)
     buf = run(solver, host, 3)
     for key in ("lamb", "iters", "status"):
         assert (buf[key].cpu().numpy()[far] == ref[key][far]).all(), key
@@ -243,7 +158,7 @@ def test_eight_step_sizes_in_two_rounds(torch_mod, merit):
     assert batch_rel_err(to_host(solver, buf["U"])[far], ref["U"][far]) < TOL_SOLVE
     np.testing.assert_allclose(buf["cost"].cpu().numpy()[far], ref["cost"][far], rtol=1e-8)
     # ... and they are not what four step sizes give
-    buf4 = run(_ls_solver(cfg, host, box, A=4, merit=merit), host, 3)
+    buf4 = run(checked_lane_solver(cfg, host, box, A=4, merit=merit), host, 3)
     assert not torch_mod.equal(buf["U"], buf4["U"])
 
 
@@ -261,8 +176,8 @@ def test_disabled_records_are_inert(torch_mod, case, layout):
     middle[:, 1] = single["obs"]
     batch = dict(host, obs=middle)
     for merit in (False, True):
-        one = _lane(cfg, single, layout=layout, merit=merit)
-        three = _lane(cfg, batch, layout=layout, merit=merit)
+        one = lane_solver(cfg, single, layout=layout, A=4, merit=merit)
+        three = lane_solver(cfg, batch, layout=layout, A=4, merit=merit)
         for n in (3, None):
             same_bits(torch_mod, run(three, batch, n), run(one, single, n), (merit, n))
 
@@ -275,9 +190,9 @@ def test_fp32_outputs_are_consistent(torch_mod, layout):
     else:
         cfg, host, box = make_case("b6_T128_K3", box=True, dtype="f32", layout=2)
     for merit in (False, True):
-        solver = _ls_solver(cfg, host, box, layout, 4, merit)
-        _check_outputs(solver, cfg, host, box, run(solver, host, 3), merit, n_iters=3)
-        _check_outputs(solver, cfg, host, box, run(solver, host, None), merit)
+        solver = checked_lane_solver(cfg, host, box, layout, 4, merit)
+        check_outputs(solver, cfg, host, box, run(solver, host, 3), merit, n_iters=3)
+        check_outputs(solver, cfg, host, box, run(solver, host, None), merit)
 
 
 def test_solve_stays_a_single_launch(torch_mod):
@@ -290,11 +205,11 @@ def test_solve_stays_a_single_launch(torch_mod):
     host = dict(host, obs=workloads.obstacles_on_path(host, 2, SEED))
     box = Box(cfg.n, {2: (0.0, 10.0)})
     for merit in (False, True):
-        solver = _ls_solver(cfg, host, box, A=4, merit=merit)
+        solver = checked_lane_solver(cfg, host, box, A=4, merit=merit)
         want = run(solver, host, None)
-        _check_outputs(solver, cfg, host, box, want, merit)
+        check_outputs(solver, cfg, host, box, want, merit)
         solver.set_compaction(64)
-        assert solver.solve_kernel(4160) == _name(host, box, merit)
+        assert solver.solve_kernel(4160) == lane_name(host, box, merit, 4)
         same_bits(torch_mod, run(solver, host, None), want)
 
 

@@ -3,29 +3,28 @@ on k_lane_iterate_merit meet the conditioning rule of the barrier-cost suite on 
 the option matters on them, the launch plan does not depend on it (i2lqr_lane_plan.hpp in a
 stand-alone program under AddressSanitizer and UBSan, as test_lane_models_host.py builds one), and
 the header, the C-ABI unit and the unit list name what they must."""
-import shutil
 import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from helpers import ST_LAMB_OVERFLOW
-from lane_merit_cases import (IDS, LAMB_OVERFLOW_EXITS, LANE_MERIT_RUNS, LANE_MERIT_TERMINATION_RUNS,
-                              LANE_MERIT_TILED, TERMINATION_IDS, lane_merit_reference)
-from opt_in_cases import MARGIN, MAX_LEFT_OUT, make_case
+from helpers import HOST_CHECK_PRELUDE, ST_LAMB_OVERFLOW, run_host_program
+from lane_cases import (LANE_MERIT_IDS, LANE_MERIT_LAMB_OVERFLOW_EXITS, LANE_MERIT_RUNS,
+                        LANE_MERIT_TERMINATION_IDS, LANE_MERIT_TERMINATION_RUNS, lane_reference)
+from opt_in_cases import MARGIN, MAX_LEFT_OUT, TILED, make_case
 from opt_in_reference import reference
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "ilqr_iterative_tasks_amd" / "csrc"
 
 
-@pytest.mark.parametrize("case,n_iters,layout", LANE_MERIT_RUNS, ids=IDS)
+@pytest.mark.parametrize("case,n_iters,layout", LANE_MERIT_RUNS, ids=LANE_MERIT_IDS)
 def test_gpu_runs_meet_the_conditioning_rule(case, n_iters, layout):
     """A problem is compared on the GPU only if its smallest deciding margin is >= 1e-7 (ten times
     the 1e-8 allowed on X and U).  A fixed-count run may leave out no problem, a termination run at
     most 20 %."""
-    margin = lane_merit_reference(case, n_iters, layout)["margin"]
+    margin = lane_reference(case, 1, n_iters, layout, merit=True)["margin"]
     out = (margin < MARGIN).mean()
     print(f"{case}: smallest margin {margin.min():.3g}, {out:.1%} of the problems below {MARGIN}")
     assert out <= MAX_LEFT_OUT[n_iters is None]
@@ -42,49 +41,34 @@ def test_the_unboxed_gpu_run_meets_the_conditioning_rule():
 
 def test_the_long_horizon_gpu_run_meets_the_conditioning_rule():
     """b4_N64 with its box, three iterations: branch words are compared on every problem."""
-    margin = lane_merit_reference("b4_N64", 3)["margin"]
+    margin = lane_reference("b4_N64", 1, 3, merit=True)["margin"]
     print(f"smallest margin {margin.min():.3g}")
     assert (margin >= MARGIN).all()
 
 
-@pytest.mark.parametrize("case,n_iters,layout", LANE_MERIT_TERMINATION_RUNS, ids=TERMINATION_IDS)
+@pytest.mark.parametrize("case,n_iters,layout", LANE_MERIT_TERMINATION_RUNS,
+                         ids=LANE_MERIT_TERMINATION_IDS)
 def test_the_option_removes_lamb_overflow_exits(case, n_iters, layout):
     """What the option is for: with the soft accept test more than a quarter of every set gives up
     with LAMB_OVERFLOW; with the barrier cost fewer do (the README's figures, box on)."""
-    merit = lane_merit_reference(case, None, layout)
-    soft = lane_merit_reference(case, None, layout, merit=False)
+    merit = lane_reference(case, 1, None, layout, merit=True)
+    soft = lane_reference(case, 1, None, layout)
     exits = tuple(int((r["status"] == ST_LAMB_OVERFLOW).sum()) for r in (soft, merit))
     print(f"{case}: LAMB_OVERFLOW exits {exits[0]} -> {exits[1]} of {len(soft['status'])}")
     assert exits[1] < exits[0]
-    assert exits == LAMB_OVERFLOW_EXITS[case]
+    assert exits == LANE_MERIT_LAMB_OVERFLOW_EXITS[case]
 
 
-@pytest.mark.parametrize("case", LANE_MERIT_TILED)
+@pytest.mark.parametrize("case", TILED)
 def test_the_option_moves_lamb_on_the_tiled_sets(case):
-    merit = lane_merit_reference(case, None, 2)
-    soft = lane_merit_reference(case, None, 2, merit=False)
+    merit = lane_reference(case, 1, None, 2, merit=True)
+    soft = lane_reference(case, 1, None, 2)
     share = (merit["lamb"] != soft["lamb"]).mean()
     print(f"{case}: lamb differs on {share:.2f} of the problems")
     assert share >= 0.5
 
 
-PROGRAM = r"""
-#include "i2lqr_lane_plan.hpp"
-
-#include <cstdio>
-#include <initializer_list>
-
-using namespace i2lqr;
-
-static int bad = 0;
-#define CHECK(cond)                                              \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      if (bad < 40) std::printf("FAILED line %d: %s\n", __LINE__, #cond); \
-      bad++;                                                     \
-    }                                                            \
-  } while (0)
-
+PROGRAM = '#include "i2lqr_lane_plan.hpp"\n' + HOST_CHECK_PRELUDE + r"""
 int main() {
   const DeviceGeometry g;  // the MI355X figures
   const LaneModel off;
@@ -129,27 +113,15 @@ int main() {
 
 
 def test_lane_model_plan_does_not_depend_on_the_barrier_cost(tmp_path):
-    cxx = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    src = tmp_path / "lane_merit_plan_check.cpp"
-    src.write_text(PROGRAM)
-    exe = tmp_path / "lane_merit_plan_check"
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
-                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    print(run.stdout, run.stderr)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "0 failed" in run.stdout
+    run_host_program(tmp_path, "lane_merit_plan_check", PROGRAM, [CSRC])
 
 
 def test_header_sources_and_units_name_the_option():
     hdr = (ROOT / "include" / "i2lqr.h").read_text()
     assert '"lane_barrier_cost"' in hdr and '"k_lane_iterate (barrier cost)"' in hdr
     assert "k_lane_iterate_merit" in hdr
-    src = (CSRC / "i2lqr_abi.hip").read_text()
-    assert '"k_lane_iterate (barrier cost)"' in src and '"lane_barrier_cost"' in src
+    assert '"lane_barrier_cost"' in (CSRC / "i2lqr_abi.hip").read_text()
+    assert '"k_lane_iterate (barrier cost)"' in (CSRC / "i2lqr_lane_opt_in.hpp").read_text()
     units = subprocess.run(["make", "-s", "-C", str(CSRC), "units"], check=True, capture_output=True,
                            text=True, timeout=60).stdout.split()
     assert "i2lqr_lane_merit_f64" in units and "i2lqr_lane_merit_f32" in units

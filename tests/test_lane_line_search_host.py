@@ -4,15 +4,14 @@ acts on them (short steps are taken, LAMB_OVERFLOW exits go), the launch plan do
 step count (i2lqr_lane_plan.hpp in a stand-alone program under AddressSanitizer and UBSan, as
 test_lane_barrier_cost_host.py builds one), and the header, the C-ABI unit, the unit list and the
 docstring of set_option name what they must."""
-import shutil
 import subprocess
 from pathlib import Path
 
 import pytest
 
-from helpers import ST_LAMB_OVERFLOW
-from lane_ls_cases import (IDS, LAMB_OVERFLOW_EXITS, LANE_LS_RUNS, LEFT_OUT, FULL_STEP_RUNS, SOFT_RUNS,
-                           WEIGHTED_B6, WEIGHTED_RUNS, lane_ls_reference, run_id)
+from helpers import HOST_CHECK_PRELUDE, ST_LAMB_OVERFLOW, run_host_program
+from lane_cases import (FULL_STEP_RUNS, LANE_LS_LAMB_OVERFLOW_EXITS, LANE_LS_RUNS, LEFT_OUT, SOFT_RUNS,
+                        WEIGHTED_B6, WEIGHTED_RUNS, lane_reference, ls_run_ids)
 from opt_in_cases import BASES, BOXES, MARGIN, MAX_LEFT_OUT, RECORDS
 from opt_in_reference import short_step_share
 
@@ -27,12 +26,12 @@ def _horizon(case):
     return BASES[RECORDS[name][0] if name in RECORDS else name][1]
 
 
-@pytest.mark.parametrize("case,A,n_iters,layout,merit", LANE_LS_RUNS, ids=IDS)
+@pytest.mark.parametrize("case,A,n_iters,layout,merit", LANE_LS_RUNS, ids=ls_run_ids(LANE_LS_RUNS))
 def test_gpu_runs_meet_the_conditioning_rule(case, A, n_iters, layout, merit):
     """A problem is compared on the GPU only if its smallest deciding margin - the argmin's among
     them - is >= 1e-7.  A fixed-count run may leave out no problem, a termination run at most 20 %;
     the counts of the termination runs are pinned."""
-    margin = lane_ls_reference(case, A, n_iters, layout, merit)["margin"]
+    margin = lane_reference(case, A, n_iters, layout, merit)["margin"]
     out = margin < MARGIN
     print(f"{case}: smallest margin {margin.min():.3g}, {out.sum()} of {len(out)} problems below {MARGIN}")
     assert out.mean() <= MAX_LEFT_OUT[n_iters is None]
@@ -47,63 +46,48 @@ def test_every_pinned_count_belongs_to_a_run():
 SOFT_LONG = [run for run in SOFT_RUNS if _horizon(run[0]) > 1] + [run for run in WEIGHTED_RUNS if not run[4]]
 
 
-@pytest.mark.parametrize("case,A,n_iters,layout,merit", SOFT_LONG, ids=[run_id(*r) for r in SOFT_LONG])
+@pytest.mark.parametrize("case,A,n_iters,layout,merit", SOFT_LONG, ids=ls_run_ids(SOFT_LONG))
 def test_short_steps_are_taken(case, A, n_iters, layout, merit):
     """The option acts: in at least 15 % of the problems of every soft run with N > 1 the reference
     chooses a step shorter than the full one at least once."""
-    share = short_step_share(lane_ls_reference(case, A, n_iters, layout, merit))
+    share = short_step_share(lane_reference(case, A, n_iters, layout, merit))
     print(f"{case} A = {A}: short steps in {share:.2f} of the problems")
     assert share >= 0.15
 
 
-@pytest.mark.parametrize("case,A,n_iters,layout,merit", FULL_STEP_RUNS,
-                         ids=[run_id(*r) for r in FULL_STEP_RUNS])
+@pytest.mark.parametrize("case,A,n_iters,layout,merit", FULL_STEP_RUNS, ids=ls_run_ids(FULL_STEP_RUNS))
 def test_the_horizon_one_merit_runs_take_full_steps_only(case, A, n_iters, layout, merit):
     """... so the GPU suite may ask for k_lane_iterate_merit's bits on them."""
-    ref = lane_ls_reference(case, A, n_iters, layout, merit)
+    ref = lane_reference(case, A, n_iters, layout, merit)
     assert len(ref["jstar"]) == n_iters and (ref["jstar"] == 0).all()
 
 
-@pytest.mark.parametrize("case,A,n_iters,layout,merit", [r for r in WEIGHTED_RUNS if r[1] == 8],
-                         ids=[run_id(*r) for r in WEIGHTED_RUNS if r[1] == 8])
+WEIGHTED_A8 = [run for run in WEIGHTED_RUNS if run[1] == 8]
+
+
+@pytest.mark.parametrize("case,A,n_iters,layout,merit", WEIGHTED_A8, ids=ls_run_ids(WEIGHTED_A8))
 def test_the_weighted_runs_reach_beyond_the_first_pass(case, A, n_iters, layout, merit):
     """bicycle6 in fp64 with stage weights runs its candidates two to a pass: at A = 8 the reference
     takes steps with j >= 4 on these sets, so the third and fourth pass decide."""
-    ref = lane_ls_reference(case, A, n_iters, layout, merit)
+    ref = lane_reference(case, A, n_iters, layout, merit)
     far = (ref["jstar"] >= 4).any(axis=0) & (ref["margin"] >= MARGIN)
     print(f"{case}: {far.sum()} compared problems take a step with j >= 4")
     assert far.mean() >= 0.25
 
 
-@pytest.mark.parametrize("case", list(LAMB_OVERFLOW_EXITS))
+@pytest.mark.parametrize("case", list(LANE_LS_LAMB_OVERFLOW_EXITS))
 def test_the_line_search_removes_lamb_overflow_exits(case):
     """What the option is for (the README's figures, box on, solves to termination): LAMB_OVERFLOW
     exits with one and with four step sizes, soft accept test and barrier cost."""
-    layout, want = LAMB_OVERFLOW_EXITS[case]
-    exits = tuple(int((lane_ls_reference(case, A, None, layout, merit)["status"] == ST_LAMB_OVERFLOW).sum())
+    layout, want = LANE_LS_LAMB_OVERFLOW_EXITS[case]
+    exits = tuple(int((lane_reference(case, A, None, layout, merit)["status"] == ST_LAMB_OVERFLOW).sum())
                   for merit in (False, True) for A in (1, 4))
     print(f"{case}: LAMB_OVERFLOW exits soft {exits[0]} -> {exits[1]}, barrier cost {exits[2]} -> {exits[3]}")
     assert exits == want
     assert exits[1] < exits[0] and exits[3] < exits[2]
 
 
-PROGRAM = r"""
-#include "i2lqr_lane_plan.hpp"
-
-#include <cstdio>
-#include <initializer_list>
-
-using namespace i2lqr;
-
-static int bad = 0;
-#define CHECK(cond)                                              \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      if (bad < 40) std::printf("FAILED line %d: %s\n", __LINE__, #cond); \
-      bad++;                                                     \
-    }                                                            \
-  } while (0)
-
+PROGRAM = '#include "i2lqr_lane_plan.hpp"\n' + HOST_CHECK_PRELUDE + r"""
 int main() {
   const DeviceGeometry g;  // the MI355X figures
   const LaneModel off;
@@ -153,27 +137,15 @@ int main() {
 
 
 def test_lane_model_plan_does_not_depend_on_the_step_count(tmp_path):
-    cxx = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    src = tmp_path / "lane_ls_plan_check.cpp"
-    src.write_text(PROGRAM)
-    exe = tmp_path / "lane_ls_plan_check"
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
-                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    print(run.stdout, run.stderr)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "0 failed" in run.stdout
+    run_host_program(tmp_path, "lane_ls_plan_check", PROGRAM, [CSRC])
 
 
 def test_header_sources_units_and_docstring_name_the_option():
     hdr = (ROOT / "include" / "i2lqr.h").read_text()
     assert '"lane_line_search"' in hdr and '"k_lane_iterate (line search)"' in hdr
     assert "k_lane_iterate_ls" in hdr
-    src = (CSRC / "i2lqr_abi.hip").read_text()
-    assert '"k_lane_iterate (line search)"' in src and '"lane_line_search"' in src
+    assert '"lane_line_search"' in (CSRC / "i2lqr_abi.hip").read_text()
+    assert '"k_lane_iterate (line search)"' in (CSRC / "i2lqr_lane_opt_in.hpp").read_text()
     units = subprocess.run(["make", "-s", "-C", str(CSRC), "units"], check=True, capture_output=True,
                            text=True, timeout=60).stdout.split()
     assert "i2lqr_lane_ls_f64" in units and "i2lqr_lane_ls_f32" in units

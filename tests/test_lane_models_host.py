@@ -1,38 +1,22 @@
 """CPU suite of "lane_models" (include/i2lqr.h): the plan of a model launch (i2lqr_lane_plan.hpp: a
-stand-alone program under AddressSanitizer and UBSan, as test_lane_plan_host.py builds one), the
-header's text, and the conditioning of the two 128-problem sets test_gpu_lane_models.py adds to the
-sets test_obstacles_host.py / test_state_box_host.py already pin."""
+stand-alone program under AddressSanitizer and UBSan, helpers.run_host_program), the forms, names and
+refusals of the lane options (i2lqr_lane_opt_in.hpp, a second such program), the header's text, and
+the conditioning of the two 128-problem sets test_gpu_lane_models.py adds to the sets
+test_obstacles_host.py / test_state_box_host.py already pin."""
 import functools
-import shutil
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+from helpers import HOST_CHECK_PRELUDE, run_host_program
 from opt_in_cases import RECORDS, TILED, TILED_RUNS, make_case
 from opt_in_reference import first_record_only, reference
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "ilqr_iterative_tasks_amd" / "csrc"
 
-PROGRAM = r"""
-#include "i2lqr_lane_plan.hpp"
-
-#include <cstdio>
-#include <initializer_list>
-
-using namespace i2lqr;
-
-static int bad = 0;
-#define CHECK(cond)                                              \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      if (bad < 40) std::printf("FAILED line %d: %s\n", __LINE__, #cond); \
-      bad++;                                                     \
-    }                                                            \
-  } while (0)
-
+PROGRAM = '#include "i2lqr_lane_plan.hpp"\n' + HOST_CHECK_PRELUDE + r"""
 static LaneShape shape(int n, int m, int N, int word, bool weights = false, int max_iter = 150) {
   return LaneShape{n, m, N, word, false, weights, max_iter};
 }
@@ -163,19 +147,202 @@ int main() {
 
 
 def test_lane_model_plan(tmp_path):
-    cxx = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    src = tmp_path / "lane_model_plan_check.cpp"
-    src.write_text(PROGRAM)
-    exe = tmp_path / "lane_model_plan_check"
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
-                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    print(run.stdout, run.stderr)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "0 failed" in run.stdout
+    run_host_program(tmp_path, "lane_model_plan_check", PROGRAM, [CSRC])
+
+
+# The form a handle's options select, its display name and every request the lane forms refuse
+# (i2lqr_lane_opt_in.hpp).  The codes and messages are literals copied from i2lqr_set_option,
+# i2lqr_set_state_box and refuse_lane_model of csrc/i2lqr_abi.hip as it stood before the rules moved
+# (commit a0281da, "Opt-in line search on the one-problem-per-lane kernel"), not from the header.
+RULES_PROGRAM = '#include "i2lqr_lane_opt_in.hpp"\n' + HOST_CHECK_PRELUDE + r"""
+static WaveModel held(int obs, bool box) {
+  WaveModel m;
+  m.obs = obs;
+  if (box) {
+    m.box.hi[2] = 10.0;
+    m.box.m_hi = 4u;
+  }
+  return m;
+}
+
+static void forms_and_names() {
+  long combos = 0;
+  for (int K : {1, 3})
+    for (bool box : {false, true})
+      for (bool merit : {false, true})
+        for (int A : {0, 2, 8}) {
+          LaneOptIn opt;
+          opt.models = true;
+          opt.barrier_cost = merit;
+          opt.line_search = A;
+          const LaneModel md = lane_model(held(K > 1 ? K : 0, box), opt);
+          combos++;
+          CHECK(md.records == K && md.box == box && md.barrier_cost == merit && md.line_search == A);
+          CHECK(md.on() == (K > 1 || box || merit || A > 1));
+          // barrier cost > box > several records > line search alone
+          const char* name = "k_lane_iterate";
+          LaneForm form = LANE_PLAIN;
+          if (A > 1) { form = LANE_LS; name = "k_lane_iterate (line search)"; }
+          if (K > 1) { form = LANE_OBS; name = "k_lane_iterate (several obstacles)"; }
+          if (box) { form = LANE_BOX; name = "k_lane_iterate (state box)"; }
+          if (merit) { form = LANE_MERIT; name = "k_lane_iterate (barrier cost)"; }
+          CHECK(md.form() == form);
+          CHECK((md.form() == LANE_PLAIN) == !md.on());
+          CHECK(!std::strcmp(lane_kernel_name(md.form()), name));
+        }
+  CHECK(combos == 2L * 2 * 2 * 3);
+  CHECK(LANE_PLAIN < LANE_LS && LANE_LS < LANE_OBS && LANE_OBS < LANE_BOX && LANE_BOX < LANE_MERIT);
+  // "obstacles" 0 / 1 are one record; a line search of 1 is none
+  CHECK(lane_model(held(1, false), LaneOptIn()).form() == LANE_PLAIN);
+  CHECK((LaneModel{1, false, false, 1}.form()) == LANE_PLAIN);
+}
+
+enum Site { MAJOR, LANE, LANE_MODELS, QUAD_MODELS };  // layout, "lane_models", plant
+
+static LaneRefusal ask(LaneAsk what, int v, Site site, int obs = 0, bool box = false,
+                       bool merit = false, int A = 0) {
+  LaneOptIn opt;
+  opt.models = site == LANE_MODELS || site == QUAD_MODELS;
+  opt.barrier_cost = merit;
+  opt.line_search = A;
+  return lane_refusal(what, v, site == MAJOR, site == QUAD_MODELS, held(obs, box), opt);
+}
+#define REFUSED(r, want_code, want_text)                                          \
+  do {                                                                            \
+    const LaneRefusal got = (r);                                                  \
+    CHECK(got.code == (want_code));                                               \
+    CHECK(!std::strcmp(got.text, (want_text)));                                   \
+    if (std::strcmp(got.text, (want_text))) std::printf("  got: %s\n", got.text); \
+  } while (0)
+#define ACCEPTED(r)                                   \
+  do {                                                \
+    const LaneRefusal got = (r);                      \
+    CHECK(got.code == 0 && got.text[0] == '\0');      \
+  } while (0)
+
+static void refusals() {
+  const int INVALID = -1, UNSUPPORTED = -2;
+  CHECK(I2LQR_ERR_INVALID == INVALID && I2LQR_ERR_UNSUPPORTED == UNSUPPORTED && I2LQR_OK == 0);
+  // a problem-major handle
+  REFUSED(ask(LANE_ASK_MODELS, 1, MAJOR), UNSUPPORTED,
+          "\"lane_models\" is built for the batch-minor / batch-tiled layouts (a problem-major "
+          "handle runs the models on the one-problem-per-wavefront kernels without it)");
+  REFUSED(ask(LANE_ASK_BARRIER_COST, 1, MAJOR), UNSUPPORTED,
+          "\"lane_barrier_cost\" is built for the batch-minor / batch-tiled layouts: a "
+          "problem-major handle takes \"barrier_cost\" (the one-problem-per-wavefront kernel)");
+  for (int A : {2, 4, 8})
+    REFUSED(ask(LANE_ASK_LINE_SEARCH, A, MAJOR), UNSUPPORTED,
+            "\"lane_line_search\" is built for the batch-minor / batch-tiled layouts: a "
+            "problem-major handle takes \"line_search\" (the one-problem-per-wavefront kernel)");
+  // ... takes records, a box and "barrier_cost" on its own kernels
+  ACCEPTED(ask(LANE_ASK_OBSTACLES, 8, MAJOR));
+  ACCEPTED(ask(LANE_ASK_BOX, 1, MAJOR));
+  ACCEPTED(ask(WAVE_ASK_BARRIER_COST, 1, MAJOR));
+  ACCEPTED(ask(LANE_ASK_MODELS, 0, MAJOR, 3, true));  // (its records and box are not "lane_models"')
+  // a lane handle without "lane_models"
+  REFUSED(ask(LANE_ASK_BARRIER_COST, 1, LANE), UNSUPPORTED,
+          "\"lane_barrier_cost\" runs on the kernel of \"lane_models\": set \"lane_models\" to 1 "
+          "first");
+  for (int A : {2, 4, 8})
+    REFUSED(ask(LANE_ASK_LINE_SEARCH, A, LANE), UNSUPPORTED,
+            "\"lane_line_search\" runs on the kernel of \"lane_models\": set \"lane_models\" to 1 "
+            "first");
+  for (int K : {2, 8})
+    REFUSED(ask(LANE_ASK_OBSTACLES, K, LANE), UNSUPPORTED,
+            "\"obstacles\" is built for the problem-major layout (the one-problem-per-wavefront "
+            "kernel)");
+  REFUSED(ask(LANE_ASK_BOX, 1, LANE), UNSUPPORTED,
+          "a state box is built for the problem-major layout (the one-problem-per-wavefront "
+          "kernel)");
+  // "barrier_cost" on a lane handle, with or without "lane_models", bicycles or quad12
+  for (Site site : {LANE, LANE_MODELS, QUAD_MODELS})
+    REFUSED(ask(WAVE_ASK_BARRIER_COST, 1, site), UNSUPPORTED,
+            "\"barrier_cost\" is built for the problem-major layout (the one-problem-per-wavefront "
+            "kernel); a batch-minor / batch-tiled handle of the bicycles has \"lane_barrier_cost\" "
+            "(with \"lane_models\" 1)");
+  // quad12 with "lane_models" 1 (the switch itself is accepted)
+  ACCEPTED(ask(LANE_ASK_MODELS, 1, QUAD_MODELS));
+  REFUSED(ask(LANE_ASK_BARRIER_COST, 1, QUAD_MODELS), UNSUPPORTED,
+          "\"lane_barrier_cost\" with \"lane_models\" is built for the bicycles' "
+          "one-problem-per-lane kernel, not for quad12's row-block kernel (k_lane_iterate_rows): "
+          "use the problem-major layout");
+  REFUSED(ask(LANE_ASK_LINE_SEARCH, 4, QUAD_MODELS), UNSUPPORTED,
+          "\"lane_line_search\" with \"lane_models\" is built for the bicycles' "
+          "one-problem-per-lane kernel, not for quad12's row-block kernel (k_lane_iterate_rows): "
+          "use the problem-major layout");
+  REFUSED(ask(LANE_ASK_OBSTACLES, 2, QUAD_MODELS), UNSUPPORTED,
+          "\"obstacles\" with \"lane_models\" is built for the bicycles' one-problem-per-lane "
+          "kernel, not for quad12's row-block kernel (k_lane_iterate_rows): use the problem-major "
+          "layout");
+  REFUSED(ask(LANE_ASK_BOX, 1, QUAD_MODELS), UNSUPPORTED,
+          "a state box with \"lane_models\" is built for the bicycles' one-problem-per-lane kernel, "
+          "not for quad12's row-block kernel (k_lane_iterate_rows): use the problem-major layout");
+  // ... and what a launch on such a plant says
+  CHECK(!std::strcmp(lane_models_rows_text(),
+                     "\"lane_models\" is built for the bicycles' one-problem-per-lane kernel, not "
+                     "for the row-block kernel of this plant (k_lane_iterate_rows): use the "
+                     "problem-major layout"));
+  // values, on every kind of handle and before anything else is looked at
+  for (Site site : {MAJOR, LANE, LANE_MODELS, QUAD_MODELS}) {
+    for (int v : {2, 7}) {
+      REFUSED(ask(LANE_ASK_MODELS, v, site), INVALID, "\"lane_models\" is 1 (on), or -1 / 0 (off)");
+      REFUSED(ask(LANE_ASK_BARRIER_COST, v, site), INVALID,
+              "\"lane_barrier_cost\" is 1 (on), or -1 / 0 (off)");
+    }
+    for (int v : {3, 5, 6, 7, 9, 16})
+      REFUSED(ask(LANE_ASK_LINE_SEARCH, v, site), INVALID,
+              "\"lane_line_search\" is 2, 4 or 8 step sizes, or -1 / 0 / 1 (off)");
+  }
+  // "lane_models" 0 / -1 while something runs on its kernel: barrier cost, then line search, then
+  // box, then records
+  const char* const merit_held = "\"lane_models\" cannot be switched off while "
+                                 "\"lane_barrier_cost\" is on: set \"lane_barrier_cost\" to 0 first";
+  const char* const ls_held = "\"lane_models\" cannot be switched off while \"lane_line_search\" "
+                              "is on: set \"lane_line_search\" to 0 first";
+  const char* const box_held = "\"lane_models\" cannot be switched off while a state box is on: "
+                               "clear it (i2lqr_set_state_box with NULL bounds) first";
+  const char* const obs_held = "\"lane_models\" cannot be switched off while \"obstacles\" is on: "
+                               "set \"obstacles\" to 1 first";
+  for (int off : {0, -1}) {
+    REFUSED(ask(LANE_ASK_MODELS, off, LANE_MODELS, 0, false, true), INVALID, merit_held);
+    REFUSED(ask(LANE_ASK_MODELS, off, LANE_MODELS, 0, false, false, 2), INVALID, ls_held);
+    REFUSED(ask(LANE_ASK_MODELS, off, LANE_MODELS, 0, true), INVALID, box_held);
+    REFUSED(ask(LANE_ASK_MODELS, off, LANE_MODELS, 2), INVALID, obs_held);
+    REFUSED(ask(LANE_ASK_MODELS, off, LANE_MODELS, 3, true, true, 8), INVALID, merit_held);
+    REFUSED(ask(LANE_ASK_MODELS, off, LANE_MODELS, 3, true, false, 8), INVALID, ls_held);
+    REFUSED(ask(LANE_ASK_MODELS, off, LANE_MODELS, 3, true), INVALID, box_held);
+    ACCEPTED(ask(LANE_ASK_MODELS, off, LANE_MODELS, 1));
+    ACCEPTED(ask(LANE_ASK_MODELS, 1, LANE_MODELS, 3, true, true, 8));  // (on stays on)
+  }
+  // the off-values are accepted everywhere
+  for (Site site : {MAJOR, LANE, LANE_MODELS, QUAD_MODELS})
+    for (int off : {0, -1}) {
+      for (LaneAsk what : {LANE_ASK_OBSTACLES, LANE_ASK_MODELS, LANE_ASK_BARRIER_COST,
+                           LANE_ASK_LINE_SEARCH, WAVE_ASK_BARRIER_COST})
+        ACCEPTED(ask(what, off, site));
+      ACCEPTED(ask(LANE_ASK_OBSTACLES, 1, site));
+      ACCEPTED(ask(LANE_ASK_LINE_SEARCH, 1, site));
+      ACCEPTED(ask(LANE_ASK_BOX, 0, site));
+    }
+  // ... and the on-values on a lane handle of the bicycles with "lane_models" 1
+  ACCEPTED(ask(LANE_ASK_MODELS, 1, LANE));
+  ACCEPTED(ask(LANE_ASK_BARRIER_COST, 1, LANE_MODELS));
+  for (int A : {2, 4, 8}) ACCEPTED(ask(LANE_ASK_LINE_SEARCH, A, LANE_MODELS));
+  for (int K : {2, 8}) ACCEPTED(ask(LANE_ASK_OBSTACLES, K, LANE_MODELS));
+  ACCEPTED(ask(LANE_ASK_BOX, 1, LANE_MODELS));
+}
+
+int main() {
+  forms_and_names();
+  refusals();
+  std::printf("%d failed\n", bad);
+  return bad ? 1 : 0;
+}
+"""
+
+
+def test_lane_forms_names_and_refusals(tmp_path):
+    run_host_program(tmp_path, "lane_opt_in_check", RULES_PROGRAM, [CSRC])
 
 
 def test_header_documents_the_option_and_the_layouts():
@@ -183,7 +350,7 @@ def test_header_documents_the_option_and_the_layouts():
     assert '"lane_models"' in hdr
     assert "obs[6][K][B]" in hdr and "obs[B/64][6][K][64]" in hdr
     assert "k_lane_iterate_model" in hdr
-    src = (CSRC / "i2lqr_abi.hip").read_text()
+    src = (CSRC / "i2lqr_lane_opt_in.hpp").read_text()
     assert '"k_lane_iterate (several obstacles)"' in src and '"k_lane_iterate (state box)"' in src
     units = (CSRC / "Makefile").read_text()
     assert "i2lqr_lane_model_f64" in units and "i2lqr_lane_model_f32" in units

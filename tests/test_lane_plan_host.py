@@ -13,31 +13,13 @@ Schedule: two literal schedules, then every combination of max_iter 1 ... 200 wi
 "first_chunk", "chunk_step", "final_round" and the three kinds of tail: no more than kMaxRounds
 rounds (one counter each), and either the chunks sum to max_iter or a tail kernel that may run
 (4 iterations done) takes every survivor."""
-import shutil
-import subprocess
 from pathlib import Path
 
-import pytest
+from helpers import HOST_CHECK_PRELUDE, run_host_program
 
 CSRC = Path(__file__).resolve().parent.parent / "ilqr_iterative_tasks_amd" / "csrc"
 
-PROGRAM = r"""
-#include "i2lqr_lane_plan.hpp"
-
-#include <cstdio>
-#include <initializer_list>
-
-using namespace i2lqr;
-
-static int bad = 0;
-#define CHECK(cond)                                              \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      if (bad < 40) std::printf("FAILED line %d: %s\n", __LINE__, #cond); \
-      bad++;                                                     \
-    }                                                            \
-  } while (0)
-
+PROGRAM = '#include "i2lqr_lane_plan.hpp"\n' + HOST_CHECK_PRELUDE + r"""
 static LaneShape shape(int n, int m, int N, int word, bool weights = false, int max_iter = 150) {
   return LaneShape{n, m, N, word, n == 12, weights, max_iter};
 }
@@ -298,16 +280,4 @@ int main() {
 
 
 def test_lane_plan_rules_against_literals(tmp_path):
-    cxx = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    src = tmp_path / "lane_plan_check.cpp"
-    src.write_text(PROGRAM)
-    exe = tmp_path / "lane_plan_check"
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
-                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    print(run.stdout, run.stderr)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "0 failed" in run.stdout
+    run_host_program(tmp_path, "lane_plan_check", PROGRAM, [CSRC])

@@ -4,31 +4,13 @@ derives from it.  The header is plain C++17: a stand-alone program that includes
 library is built with the host compiler under AddressSanitizer and UBSan and run.  The expected
 values are literals: the precedence box > obstacles > line search, the step and record counts, and
 the LDS behind a problem's slice - 0, then 6 K words, then 6 K + 2 n (N + 1) + 2 n words."""
-import shutil
-import subprocess
 from pathlib import Path
 
-import pytest
+from helpers import HOST_CHECK_PRELUDE, run_host_program
 
 CSRC = Path(__file__).resolve().parent.parent / "ilqr_iterative_tasks_amd" / "csrc"
 
-PROGRAM = r"""
-#include "i2lqr_wave_model.hpp"
-
-#include <cstdio>
-#include <cstring>
-
-using namespace i2lqr;
-
-static int bad = 0;
-#define CHECK(cond)                                              \
-  do {                                                           \
-    if (!(cond)) {                                               \
-      std::printf("FAILED line %d: %s\n", __LINE__, #cond);      \
-      bad++;                                                     \
-    }                                                            \
-  } while (0)
-
+PROGRAM = '#include "i2lqr_wave_model.hpp"\n' + HOST_CHECK_PRELUDE + r"""
 static WaveModel model(int ls, int obs, bool box) {
   WaveModel m;
   m.ls = ls;
@@ -106,16 +88,4 @@ int main() {
 
 
 def test_wave_model_rules_against_literals(tmp_path):
-    cxx = next((c for c in ("c++", "g++", "clang++") if shutil.which(c)), None)
-    if cxx is None:
-        pytest.skip("no host C++ compiler")
-    src = tmp_path / "wave_model_check.cpp"
-    src.write_text(PROGRAM)
-    exe = tmp_path / "wave_model_check"
-    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-I{CSRC}",
-                    "-o", str(exe), str(src)], check=True, capture_output=True, timeout=300)
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
-    print(run.stdout, run.stderr)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert "0 failed" in run.stdout
+    run_host_program(tmp_path, "wave_model_check", PROGRAM, [CSRC])
