@@ -13,7 +13,7 @@ import numpy as np
 from helpers import ROLLOUT_TOL, TOL_SOLVE, batch_rel_err, dev_batch, to_host
 from lane_cases import lane_reference
 from opt_in_cases import make_case, on_layout
-from opt_in_reference import OUTPUTS, penalty  # noqa: F401 (the suites take OUTPUTS from here)
+from opt_in_reference import OUTPUTS, penalty, step_batch, step_index  # noqa: F401 (the suites take OUTPUTS from here)
 
 # the kernels' display names (csrc/i2lqr_wave_model.hpp, csrc/i2lqr_abi.hip)
 LS_NAME = "k_iterate (line search)"
@@ -83,6 +83,31 @@ def compare(solver, buf, ref, n_iters, gains=True):
         assert batch_rel_err(to_host(solver, buf["K"])[same], ref["K"][same]) < 1e-7
         assert batch_rel_err(to_host(solver, buf["k"])[same], ref["k"][same], floor=1.0) < 1e-7
     return same
+
+
+# A chain of dependent solves ("wave_chain") as single launches
+
+
+def step_major(host, chains, chain_len):
+    """The chain-major batch with step c's problems side by side: problem c * chains + a is
+    candidate c of chain a."""
+    idx = np.concatenate([step_index(chains, chain_len, c) for c in range(chain_len)])
+    return step_batch(host, idx), idx
+
+
+def step_by_step(solver, host, chains, chain_len):
+    """chain_len calls of solve() over consecutive slices of one step-major buffer set, lamb copied
+    from step to step.  Returns the buffers in chain-major order."""
+    import torch
+    stepped, idx = step_major(host, chains, chain_len)
+    buf = dev_batch(solver, stepped)
+    for c in range(chain_len):
+        view = {key: None if t is None else t[c * chains:(c + 1) * chains] for key, t in buf.items()}
+        if c > 0:
+            view["lamb"].copy_(buf["lamb"][(c - 1) * chains:c * chains])
+        solver.solve(view)
+    back = torch.as_tensor(np.argsort(idx), device=solver.device)
+    return {key: None if t is None else t.index_select(0, back) for key, t in buf.items()}
 
 
 # The lane forms ("lane_models", "lane_barrier_cost", "lane_line_search": k_lane_iterate_model / _merit

@@ -10,8 +10,8 @@ reference's own output by 3.4e-9 (chaotic amplification through up to 150 iterat
 import numpy as np
 import pytest
 
-from helpers import (TOL_SOLVE, batch_rel_err, check_solve_outputs, dev_batch, problems_from_calls,
-                     rel_err, to_dev, to_host)
+from helpers import (TOL_SOLVE, batch_rel_err, check_flipped, check_solve_against_calls,
+                     check_solve_outputs, dev_batch, rel_err, to_dev, to_host)
 
 pytestmark = pytest.mark.gpu
 
@@ -84,19 +84,7 @@ def test_backward_forward_match_reference_g1(torch_mod, golden_dir, layout):
 
 def _check_solve_against_calls(g, N, layout, tol=TOL_SOLVE, max_flips=0):
     solver, cfg = make_solver("bicycle4", N, layout=layout)
-    host = problems_from_calls(g, N)
-    buf = solver.solve(dev_batch(solver, host))
-    iters = buf["iters"].cpu().numpy()
-    lamb = buf["lamb"].cpu().numpy()
-    same = (iters == g["iters"]) & (lamb == g["lamb_out"])
-    flips = int((~same).sum())
-    assert flips <= max_flips, f"{flips} calls took a different branch: {np.nonzero(~same)[0][:8]}"
-    U, X = to_host(solver, buf["U"])[same], to_host(solver, buf["X"])[same]
-    # U lives in the input box |u| <= u_max ~ 2: a solution that is numerically zero (|U| ~ 1e-7)
-    # is compared at the scale floor 1e-2, not relative to its own round-off-sized entries
-    assert batch_rel_err(U, g["U"][same], floor=1e-2) < tol
-    assert batch_rel_err(X, g["X"][same]) < tol
-    return buf
+    return check_solve_against_calls(solver, g, N, tol, max_flips)
 
 
 def test_solve_matches_reference_g2(torch_mod, golden_dir, layout):
@@ -185,24 +173,6 @@ def test_function_level_vs_oracle(torch_mod, system, N, dt, B, layout):
     np.testing.assert_allclose(cn.cpu().numpy(), cn_o, rtol=1e-10)
 
 
-def _check_flipped(buf, ref, same, cost_tol, early_exit):
-    """Problems whose accept / reject history differs from the oracle's (a cost comparison decided
-    at round-off level went the other way) are excluded from the trajectory comparison — but not
-    from scrutiny: the branch that was taken instead must be as good.  Their returned cost must
-    agree with the oracle's to `cost_tol` (relative) and their status must be a legal exit of the
-    entry point: CONVERGED, MAX_ITER or LAMB_OVERFLOW after a solve (`early_exit`), RUNNING,
-    CONVERGED or LAMB_OVERFLOW after a fixed-count iterate (orc_ilqr never returns MAX_ITER there)."""
-    if same.all():
-        return
-    cost = buf["cost"].double().cpu().numpy()[~same]
-    want = ref["cost"][~same]
-    assert np.isfinite(cost).all()
-    rel = np.abs(cost - want) / np.maximum(np.abs(want), 1e-300)
-    assert rel.max() <= cost_tol, f"flipped problems: cost off by {rel.max():.3e} (> {cost_tol})"
-    st = buf["status"].cpu().numpy()[~same]
-    assert set(np.unique(st)) <= ({1, 2, 3} if early_exit else {0, 1, 3}), np.unique(st)
-
-
 @pytest.mark.parametrize("system,N,dt,B,iters", [("bicycle6", 20, 0.25, 1024, 10),
                                                  ("bicycle4", 6, 1.0, 512, 10),
                                                  ("quad12", 50, 0.02, 64, 4)])
@@ -221,7 +191,7 @@ def test_iterate_vs_oracle(torch_mod, system, N, dt, B, iters, layout):
     # an accept/reject decided by a cost difference at round-off level may flip; it must be rare
     assert same.mean() > 0.99, f"{(~same).sum()} of {B} problems took a different branch"
     # ... and where it flips the two branches are equally good: same cost to 1e-6
-    _check_flipped(buf, ref, same, 1e-6, early_exit=False)
+    check_flipped(buf, ref, same, 1e-6, early_exit=False)
     assert (buf["status"].cpu().numpy()[same] == ref["status"][same]).all()
     for key in ("X", "U"):
         assert batch_rel_err(to_host(solver, buf[key])[same], ref[key][same]) < TOL_SOLVE, key
@@ -245,7 +215,7 @@ def test_solve_vs_oracle_bicycle6(torch_mod, layout):
     assert same.mean() > 0.98
     # a flipped problem may stop one iteration earlier or later than the oracle: its cost is then
     # within the convergence threshold eps (control/iterative_ilqr.py:78) of the oracle's
-    _check_flipped(buf, ref, same, cfg.eps, early_exit=True)
+    check_flipped(buf, ref, same, cfg.eps, early_exit=True)
     assert (buf["status"].cpu().numpy()[same] == ref["status"][same]).all()
     assert batch_rel_err(to_host(solver, buf["X"])[same], ref["X"][same]) < TOL_SOLVE
     assert batch_rel_err(to_host(solver, buf["U"])[same], ref["U"][same]) < 1e-7
@@ -456,7 +426,7 @@ def test_config4_sizes_properties_and_oracle_sample(torch_mod, lay, B):
     sub = {key: a[key][tidx] for key in ("lamb", "cost", "status")}
     same = sub["lamb"].cpu().numpy() == ref["lamb"]
     assert same.mean() > 0.99
-    _check_flipped(sub, ref, same, 1e-6, early_exit=False)
+    check_flipped(sub, ref, same, 1e-6, early_exit=False)
     for key in ("X", "U"):
         assert batch_rel_err(got[key][same], ref[key][same]) < TOL_SOLVE, key
     np.testing.assert_allclose(sub["cost"].cpu().numpy()[same], ref["cost"][same], rtol=1e-7)
@@ -473,7 +443,7 @@ def test_config4_sizes_properties_and_oracle_sample(torch_mod, lay, B):
     it = s["iters"][tidx].cpu().numpy()
     same = (it == ref["iters"]) & (s["lamb"][tidx].cpu().numpy() == ref["lamb"])
     assert same.mean() > 0.98
-    _check_flipped({key: s[key][tidx] for key in ("cost", "status")},
+    check_flipped({key: s[key][tidx] for key in ("cost", "status")},
                    ref, same, cfg.eps, early_exit=True)
     Xs = solver.to_problem_major(s["X"])[tidx].cpu().numpy()
     assert batch_rel_err(Xs[same], ref["X"][same]) < TOL_SOLVE
@@ -876,7 +846,7 @@ def test_quad12_sixteen_lane_kernel_vs_oracle_and_wave_kernel(torch_mod, B, iter
         check_solve_outputs(solver, cfg, host, so)
         same = it["lamb"].cpu().numpy() == ref_it["lamb"]
         assert same.mean() >= 0.97, (lanes, same.mean())
-        _check_flipped(it, ref_it, same, 1e-6, early_exit=False)
+        check_flipped(it, ref_it, same, 1e-6, early_exit=False)
         for key in ("X", "U"):
             assert batch_rel_err(to_host(solver, it[key])[same], ref_it[key][same]) < TOL_SOLVE, (lanes, key)
         np.testing.assert_allclose(it["cost"].cpu().numpy()[same], ref_it["cost"][same], rtol=1e-7)
@@ -884,7 +854,7 @@ def test_quad12_sixteen_lane_kernel_vs_oracle_and_wave_kernel(torch_mod, B, iter
         assert batch_rel_err(to_host(solver, it["k"])[same], ref_it["k"][same], floor=1.0) < 1e-6
         same = (so["iters"].cpu().numpy() == ref_so["iters"]) & (so["lamb"].cpu().numpy() == ref_so["lamb"])
         assert same.mean() >= 0.97, (lanes, same.mean())
-        _check_flipped(so, ref_so, same, cfg.eps, early_exit=True)
+        check_flipped(so, ref_so, same, cfg.eps, early_exit=True)
         assert (so["status"].cpu().numpy()[same] == ref_so["status"][same]).all()
         assert batch_rel_err(to_host(solver, so["X"])[same], ref_so["X"][same]) < TOL_SOLVE, lanes
     # without a registered workspace the automatic choice is the one-problem-per-wavefront kernel
@@ -989,7 +959,7 @@ def test_quad12_full_size_properties_and_oracle_sample(torch_mod):
     tidx = torch.as_tensor(idx, device=solver.device)
     same = a["lamb"][tidx].cpu().numpy() == ref["lamb"]
     assert same.mean() >= 0.97
-    _check_flipped({key: a[key][tidx] for key in ("cost", "status")},
+    check_flipped({key: a[key][tidx] for key in ("cost", "status")},
                    ref, same, 1e-6, early_exit=False)
     for key in ("X", "U"):
         assert batch_rel_err(a[key][tidx].cpu().numpy()[same], ref[key][same]) < TOL_SOLVE, key
@@ -1022,7 +992,7 @@ def test_quad12_one_problem_per_lane_kernel_vs_oracle(torch_mod, layout_id, B):
     check_solve_outputs(solver, cfg, host, so)
     same = it["lamb"].cpu().numpy() == ref_it["lamb"]
     assert same.mean() >= 0.97, same.mean()
-    _check_flipped(it, ref_it, same, 1e-6, early_exit=False)
+    check_flipped(it, ref_it, same, 1e-6, early_exit=False)
     for key in ("X", "U"):
         assert batch_rel_err(to_host(solver, it[key])[same], ref_it[key][same]) < TOL_SOLVE, key
     np.testing.assert_allclose(it["cost"].cpu().numpy()[same], ref_it["cost"][same], rtol=1e-7)
@@ -1030,7 +1000,7 @@ def test_quad12_one_problem_per_lane_kernel_vs_oracle(torch_mod, layout_id, B):
     assert batch_rel_err(to_host(solver, it["k"])[same], ref_it["k"][same], floor=1.0) < 1e-6
     same = (so["iters"].cpu().numpy() == ref_so["iters"]) & (so["lamb"].cpu().numpy() == ref_so["lamb"])
     assert same.mean() >= 0.97, same.mean()
-    _check_flipped(so, ref_so, same, cfg.eps, early_exit=True)
+    check_flipped(so, ref_so, same, cfg.eps, early_exit=True)
     assert (so["status"].cpu().numpy()[same] == ref_so["status"][same]).all()
     assert batch_rel_err(to_host(solver, so["X"])[same], ref_so["X"][same]) < TOL_SOLVE
     # replay properties: 2 + 2 fused iterations == 4, returned X is the rollout of returned U
@@ -1083,7 +1053,7 @@ def test_quad12_full_size_on_the_lane_kernel(torch_mod):
     pm = {key: solver.to_problem_major(a[key])[tidx].cpu().numpy() for key in ("X", "U", "K", "k")}
     same = a["lamb"][tidx].cpu().numpy() == ref["lamb"]
     assert same.mean() >= 0.97
-    _check_flipped({key: a[key][tidx] for key in ("cost", "status")},
+    check_flipped({key: a[key][tidx] for key in ("cost", "status")},
                    ref, same, 1e-6, early_exit=False)
     for key in ("X", "U"):
         assert batch_rel_err(pm[key][same], ref[key][same]) < TOL_SOLVE, key
@@ -1096,7 +1066,7 @@ def test_quad12_full_size_on_the_lane_kernel(torch_mod):
                          host["lamb"][idx], host["obs"][idx])
     same = (so["iters"][tidx].cpu().numpy() == ref["iters"]) & (so["lamb"][tidx].cpu().numpy() == ref["lamb"])
     assert same.mean() >= 0.97
-    _check_flipped({key: so[key][tidx] for key in ("cost", "status")},
+    check_flipped({key: so[key][tidx] for key in ("cost", "status")},
                    ref, same, cfg.eps, early_exit=True)
     assert (so["status"][tidx].cpu().numpy()[same] == ref["status"][same]).all()
     Xs = solver.to_problem_major(so["X"])[tidx].cpu().numpy()
@@ -1368,7 +1338,7 @@ def test_inputs_outside_the_benchmark_distribution_vs_oracle(torch_mod, layout):
     it, st = buf["iters"].cpu().numpy(), buf["status"].cpu().numpy()
     same = (it == ref["iters"]) & (buf["lamb"].cpu().numpy() == ref["lamb"])
     assert same.mean() > 0.97, same.mean()
-    _check_flipped(buf, ref, same, cfg.eps, early_exit=True)
+    check_flipped(buf, ref, same, cfg.eps, early_exit=True)
     assert (st[same] == ref["status"][same]).all()
     assert set(np.unique(st)) <= {1, 2, 3}
     assert (ref["lamb"] > cfg.max_lamb).any() and (ref["iters"] == 1).any()

@@ -15,7 +15,7 @@ import pytest
 
 from helpers import check_solve_outputs, dev_batch
 from opt_in_cases import CHAIN_REFERENCE_SHAPES, CHAIN_SHAPES, make_case, make_chain
-from opt_in_gpu import OUTPUTS, compare, make_solver, options_for, same_bits
+from opt_in_gpu import OUTPUTS, compare, make_solver, options_for, same_bits, step_by_step
 from opt_in_reference import (LAP_STEPS_LIMIT, LAP_STEPS_TWO, SPEED_LIMIT, controlled_laps,
                               golden_laps, reference, step_batch, step_index, two_obstacle_set)
 
@@ -41,28 +41,6 @@ def _solver(cfg, host, box=None, A=1, wave_chain=1, **options):
     return make_solver(cfg, box, **first, **options, **models)
 
 
-def _step_major(host, chains, chain_len):
-    """The chain-major batch with step c's problems side by side: problem c * chains + a is
-    candidate c of chain a."""
-    idx = np.concatenate([step_index(chains, chain_len, c) for c in range(chain_len)])
-    return step_batch(host, idx), idx
-
-
-def _step_by_step(solver, host, chains, chain_len):
-    """chain_len calls of solve() over consecutive slices of one step-major buffer set, lamb copied
-    from step to step.  Returns the buffers in chain-major order."""
-    import torch
-    stepped, idx = _step_major(host, chains, chain_len)
-    buf = dev_batch(solver, stepped)
-    for c in range(chain_len):
-        view = {key: None if t is None else t[c * chains:(c + 1) * chains] for key, t in buf.items()}
-        if c > 0:
-            view["lamb"].copy_(buf["lamb"][(c - 1) * chains:c * chains])
-        solver.solve(view)
-    back = torch.as_tensor(np.argsort(idx), device=solver.device)
-    return {key: None if t is None else t.index_select(0, back) for key, t in buf.items()}
-
-
 def _carried(host, buf, chains, chain_len):
     """The batch with the lamb every problem started from: the first of a chain its own, the others
     what the launch wrote for the problem before (check_solve_outputs reads the lamb history)."""
@@ -77,7 +55,7 @@ def _both(name, dtype="f64"):
     cfg, host, box, A, chains, chain_len = make_chain(name, dtype)
     solver = _solver(cfg, host, box, A)
     chained = solver.solve_chained(dev_batch(solver, host), chains, chain_len)
-    return solver, cfg, host, chained, _step_by_step(solver, host, chains, chain_len)
+    return solver, cfg, host, chained, step_by_step(solver, host, chains, chain_len)
 
 
 def test_the_option_is_there_and_a_boxed_chain_runs(torch_mod):
@@ -218,7 +196,7 @@ def test_fp32_chain(torch_mod):
     solver = _solver(cfg, host, box)
     chained = solver.solve_chained(dev_batch(solver, host), 2, 3)
     check_solve_outputs(solver, cfg, _carried(host, chained, 2, 3), chained)
-    same_bits(torch_mod, chained, _step_by_step(solver, host, 2, 3), "fp32")
+    same_bits(torch_mod, chained, step_by_step(solver, host, 2, 3), "fp32")
 
 
 def test_controller_laps_in_one_launch_per_round(torch_mod):
