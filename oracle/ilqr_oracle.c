@@ -2,7 +2,7 @@
  * ilqr_oracle.c — TEST INFRASTRUCTURE, NOT PRODUCT CODE.
  *
  * A plain-C, single-thread, fp64 restatement of the reference's iLQR hot path
- * (HybridRobotics/ilqr-iterative-tasks).  Only tests/, __graft_entry__.smoke() and the
+ * (HybridRobotics/ilqr-iterative-tasks); with -DORC_F32 the same text in float (below).  Only tests/, __graft_entry__.smoke() and the
  * `cpu_baseline` leg of bench.py may load it; nothing under ilqr_iterative_tasks_amd/ does.
  *
  * Parity status: PINNED at n=4, m=2 (system bicycle4) against golden vectors captured by running
@@ -17,6 +17,9 @@
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
+#ifdef _OPENMP
+#include <omp.h>
+#endif
 
 #include "../include/i2lqr.h"
 
@@ -24,7 +27,29 @@
 #define MAXM I2LQR_MAX_M
 #define MAXH I2LQR_MAX_HORIZON
 
+#ifndef ORC_F32
 typedef i2lqr_config cfg_t;
+#else
+/*
+ * The single-precision build (libilqr_oracle_f32*.so; oracle/Makefile): the yardstick of the fp32
+ * kernels (tests/fp32_cases.py).  The same text computes in float: every header is included
+ * above, behind this point the word `double` reads `float`, <tgmath.h> sends sin / cos / exp /
+ * sqrt / fabs to their float forms by the type of the argument, -fsingle-precision-constant
+ * (set by the Makefile: without it every literal drags its expression back to double) makes
+ * the literals float, and the configuration is a float mirror of i2lqr_config (same fields, same
+ * order: oracle.py fills it), so that no constant enters as a double either.  Every exported
+ * function then takes float arrays and float scalars.
+ */
+#include <tgmath.h>
+#define double float
+typedef struct {
+  int32_t struct_size, n, m, N, dtype, layout, system_id, max_iter;
+  double dt, eps, lamb_factor, max_lamb, ctrl_q1, ctrl_q2, obs_q1, obs_q2, safety_margin;
+  double u_max[I2LQR_MAX_M], xtarget[I2LQR_MAX_N];
+  double Q[I2LQR_MAX_N * I2LQR_MAX_N], Qt[I2LQR_MAX_N * I2LQR_MAX_N], R[I2LQR_MAX_M * I2LQR_MAX_M];
+  double sys_par[8];
+} cfg_t;
+#endif
 
 /* ------------------------------------------------------------------------------------------ */
 /* Plant models                                                                               */
@@ -718,8 +743,8 @@ int orc_round_size(void) { return (int)sizeof(i2lqr_round); }  /* tests/test_abi
 
 /* Threads used by orc_ilqr_batch (OpenMP); 0 restores the runtime default.  Returns the count in
  * effect. */
+int orc_real_size(void) { return (int)sizeof(double); } /* 8, or 4 in the single-precision build */
 #ifdef _OPENMP
-#include <omp.h>
 int orc_set_threads(int n) {
   if (n > 0) omp_set_num_threads(n);
   return omp_get_max_threads();

@@ -19,15 +19,22 @@ from ilqr_iterative_tasks_amd._abi import I2lqrConfig, OBS_WORDS
 
 _DIR = Path(__file__).resolve().parent
 _SO = _DIR / "_build" / "libilqr_oracle.so"
+# precision -> library.  "f64" is the oracle.  "f32" and "f32_fast" are single-precision builds of
+# the same file (oracle/Makefile), the yardstick of the fp32 kernels (tests/fp32_cases.py): only
+# the batched entry points below take them.
+_SOS = {"f64": _SO, "f32": _DIR / "_build" / "libilqr_oracle_f32.so",
+        "f32_fast": _DIR / "_build" / "libilqr_oracle_f32_fast.so"}
 _lib = None
+_libs32 = {}
 
 
 def build(force: bool = False) -> Path:
     """Compile ilqr_oracle.c with gcc (make -C oracle)."""
     src = _DIR / "ilqr_oracle.c"
     hdr = _DIR.parent / "include" / "i2lqr.h"
-    stale = (not _SO.exists()) or any(
-        p.exists() and p.stat().st_mtime > _SO.stat().st_mtime for p in (src, hdr))
+    stale = any((not so.exists()) or any(
+        p.exists() and p.stat().st_mtime > so.stat().st_mtime for p in (src, hdr))
+        for so in _SOS.values())
     if force or stale:
         subprocess.run(["make", "-C", str(_DIR)] + (["-B"] if force else []), check=True,
                        capture_output=True)
@@ -54,6 +61,59 @@ def lib() -> C.CDLL:
         _lib.orc_config_size.restype = C.c_int
         assert _lib.orc_config_size() == C.sizeof(I2lqrConfig), "config struct drift"
     return _lib
+
+
+class _ConfigF32(C.Structure):
+    """cfg_t of the single-precision builds: i2lqr_config with every double a float."""
+    _fields_ = [(nm, {C.c_double: C.c_float}.get(tp) or
+                 (C.c_float * tp._length_ if getattr(tp, "_type_", None) is C.c_double else tp))
+                for nm, tp in I2lqrConfig._fields_]
+
+
+def _lib32(precision: str) -> C.CDLL:
+    if precision not in _libs32:
+        so = _SOS[precision]  # KeyError: not a precision
+        if not so.exists():
+            build()
+        lb = C.CDLL(str(so))
+        lb.orc_config_size.restype = C.c_int
+        lb.orc_real_size.restype = C.c_int
+        assert lb.orc_real_size() == 4, f"{so.name} was not built in single precision"
+        assert lb.orc_config_size() == C.sizeof(_ConfigF32), "float config struct drift"
+        _libs32[precision] = lb
+    return _libs32[precision]
+
+
+def _cfg32(cfg: I2lqrConfig) -> _ConfigF32:
+    """cfg rounded to float, field by field (struct_size: the mirror's own)."""
+    out = _ConfigF32()
+    for nm, tp in I2lqrConfig._fields_:
+        val = getattr(cfg, nm)
+        if hasattr(tp, "_length_"):
+            getattr(out, nm)[:] = val[:]
+        else:
+            setattr(out, nm, val)
+    out.struct_size = C.sizeof(_ConfigF32)
+    return out
+
+
+def _side(cfg: I2lqrConfig, precision: str):
+    """(library, config to pass by reference, array dtype) of a batched call."""
+    if precision == "f64":
+        return lib(), cfg, np.float64
+    return _lib32(precision), _cfg32(cfg), np.float32
+
+
+def _arr(a, dt, shape=None):
+    a = np.ascontiguousarray(a, dtype=dt)
+    if shape is not None:
+        assert a.shape == tuple(shape), (a.shape, shape)
+    return a
+
+
+def _out(a):
+    """Results come back as float64 arrays (holding the float values of a single-precision run)."""
+    return None if a is None else np.asarray(a, dtype=np.float64)
 
 
 def set_threads(n: int) -> int:
@@ -178,57 +238,65 @@ def quu_inverse_reg(Quu, lamb):
 # -- batched API (problem-major) ------------------------------------------------------------------
 
 def ilqr_batch(cfg: I2lqrConfig, X, U, x_term, lamb, obs=None, max_iter=None, early_exit=True,
-               want_gains=True):
+               want_gains=True, precision="f64"):
     """B independent ilqr() solves.  X[B,n,N+1] (x0 in [:, :, 0]), U[B,m,N], x_term[B,n], lamb[B],
-    obs[B,6] | None.  Returns dict of fresh arrays; inputs are not modified."""
+    obs[B,6] | None.  Returns dict of fresh arrays; inputs are not modified.
+    precision (here and in the three calls below): "f64", the oracle; "f32" / "f32_fast": the
+    single-precision builds - arrays and cfg are rounded to float on the way in and every float
+    result comes back as a float64 array holding the float values."""
     n, m, N = cfg.n, cfg.m, cfg.N
-    X = _f64(X).copy()
+    lb, c, dt = _side(cfg, precision)
+    X = _arr(X, dt).copy()
     B = X.shape[0]
-    U = _f64(U, (B, m, N)).copy()
-    lamb = _f64(lamb, (B,)).copy()
-    x_term = _f64(x_term, (B, n))
-    o = None if obs is None else _f64(obs, (B, OBS_WORDS))
-    K = np.zeros((B, m, n, N)) if want_gains else None
-    k = np.zeros((B, m, N)) if want_gains else None
-    cost = np.zeros(B)
+    U = _arr(U, dt, (B, m, N)).copy()
+    lamb = _arr(lamb, dt, (B,)).copy()
+    x_term = _arr(x_term, dt, (B, n))
+    o = None if obs is None else _arr(obs, dt, (B, OBS_WORDS))
+    K = np.zeros((B, m, n, N), dt) if want_gains else None
+    k = np.zeros((B, m, N), dt) if want_gains else None
+    cost = np.zeros(B, dt)
     iters = np.zeros(B, np.int32)
     status = np.zeros(B, np.int32)
-    lib().orc_ilqr_batch(C.byref(cfg), C.c_int64(B),
-                         int(cfg.max_iter if max_iter is None else max_iter),
-                         int(bool(early_exit)), _p(X), _p(U), _p(x_term), _p(lamb), _p(o), _p(K),
-                         _p(k), _p(cost), _p(iters), _p(status))
-    return dict(X=X, U=U, lamb=lamb, K=K, k=k, cost=cost, iters=iters, status=status)
+    lb.orc_ilqr_batch(C.byref(c), C.c_int64(B),
+                      int(cfg.max_iter if max_iter is None else max_iter),
+                      int(bool(early_exit)), _p(X), _p(U), _p(x_term), _p(lamb), _p(o), _p(K),
+                      _p(k), _p(cost), _p(iters), _p(status))
+    return dict(X=_out(X), U=_out(U), lamb=_out(lamb), K=_out(K), k=_out(k), cost=_out(cost),
+                iters=iters, status=status)
 
 
-def rollout_batch(cfg, X, U, x_term):
-    X = _f64(X).copy()
-    U = _f64(U).copy()
-    cost = np.zeros(X.shape[0])
-    lib().orc_rollout_batch(C.byref(cfg), C.c_int64(X.shape[0]), _p(X), _p(U), _p(_f64(x_term)),
-                            _p(cost))
-    return X, U, cost
+def rollout_batch(cfg, X, U, x_term, precision="f64"):
+    lb, c, dt = _side(cfg, precision)
+    X = _arr(X, dt).copy()
+    U = _arr(U, dt).copy()
+    cost = np.zeros(X.shape[0], dt)
+    lb.orc_rollout_batch(C.byref(c), C.c_int64(X.shape[0]), _p(X), _p(U), _p(_arr(x_term, dt)),
+                         _p(cost))
+    return _out(X), _out(U), _out(cost)
 
 
-def backward_batch(cfg, X, U, x_term, lamb, obs=None):
-    X = _f64(X)
+def backward_batch(cfg, X, U, x_term, lamb, obs=None, precision="f64"):
+    lb, c, dt = _side(cfg, precision)
+    X = _arr(X, dt)
     B = X.shape[0]
-    K = np.zeros((B, cfg.m, cfg.n, cfg.N))
-    k = np.zeros((B, cfg.m, cfg.N))
-    o = None if obs is None else _f64(obs, (B, OBS_WORDS))
-    lib().orc_backward_batch(C.byref(cfg), C.c_int64(B), _p(X), _p(_f64(U)), _p(_f64(x_term)),
-                             _p(_f64(lamb, (B,))), _p(o), _p(K), _p(k))
-    return k, K
+    K = np.zeros((B, cfg.m, cfg.n, cfg.N), dt)
+    k = np.zeros((B, cfg.m, cfg.N), dt)
+    o = None if obs is None else _arr(obs, dt, (B, OBS_WORDS))
+    lb.orc_backward_batch(C.byref(c), C.c_int64(B), _p(X), _p(_arr(U, dt)), _p(_arr(x_term, dt)),
+                          _p(_arr(lamb, dt, (B,))), _p(o), _p(K), _p(k))
+    return _out(k), _out(K)
 
 
-def forward_batch(cfg, X, U, x_term, K, k):
-    X = _f64(X)
+def forward_batch(cfg, X, U, x_term, K, k, precision="f64"):
+    lb, c, dt = _side(cfg, precision)
+    X = _arr(X, dt)
     B = X.shape[0]
     Xn = np.zeros_like(X)
-    Un = np.zeros((B, cfg.m, cfg.N))
-    cost = np.zeros(B)
-    lib().orc_forward_batch(C.byref(cfg), C.c_int64(B), _p(X), _p(_f64(U)), _p(_f64(x_term)),
-                            _p(_f64(K)), _p(_f64(k)), _p(Xn), _p(Un), _p(cost))
-    return Xn, Un, cost
+    Un = np.zeros((B, cfg.m, cfg.N), dt)
+    cost = np.zeros(B, dt)
+    lb.orc_forward_batch(C.byref(c), C.c_int64(B), _p(X), _p(_arr(U, dt)), _p(_arr(x_term, dt)),
+                         _p(_arr(K, dt)), _p(_arr(k, dt)), _p(Xn), _p(Un), _p(cost))
+    return _out(Xn), _out(Un), _out(cost)
 
 
 def relax_cost_batch(cfg, X, x_term, qfun, outer_iter, max_relax_iter=55):

@@ -18,34 +18,13 @@ import pytest
 
 import config_cases as cc
 from config_cases import COST_RATIO, FIXED, LAMB_CASES, MULTI, bound, per_problem
+from kernel_families import BICYCLE_FAMILIES, assert_within, families, family_solver
 from helpers import (check_flipped, check_solve_against_calls, check_solve_outputs, dev_batch,
                      g9_set, to_dev, to_host)
 
 pytestmark = pytest.mark.gpu
 
 KEYS = ("X", "U", "K", "k", "lamb", "cost", "iters", "status")
-# family -> (layout id, options, what iterate_kernel must name): as test_gpu_parity.py and
-# tools/parity_campaign.py pin them
-BICYCLE_FAMILIES = {
-    "wave": (0, {"group_lanes": 64}, "k_iterate"),
-    "group": (0, {"group_lanes": 8, "speculate": 0, "group_workspace": 0}, "k_group_iterate"),
-    "group-ws": (0, {"group_lanes": 8, "speculate": 0, "group_workspace": 1},
-                 "k_group_iterate (workspace form)"),
-    "spec": (0, {"group_lanes": 8, "speculate": 1}, "k_group_spec"),
-    "row16": (0, {"group_lanes": 16, "speculate": 0}, "k_group_iterate (sixteen lanes)"),
-    "lane": (1, {}, ("k_lane_iterate", "k_lane_iterate_pair")),
-    "tiled": (2, {}, ("k_lane_iterate", "k_lane_iterate_pair")),
-}
-QUAD_FAMILIES = {
-    "wave": (0, {"group_lanes": 64}, "k_iterate"),
-    "quad16": (0, {"group_lanes": 16}, "k_quad_iterate"),
-    "lane": (1, {}, "k_lane_iterate_rows"),
-    "tiled": (2, {}, "k_lane_iterate_rows"),
-}
-
-
-def families(plant):
-    return QUAD_FAMILIES if plant == "quad12" else BICYCLE_FAMILIES
 
 
 def runs(cases):
@@ -60,34 +39,8 @@ def torch_mod():
     return torch
 
 
-def family_solver(cfg, plant, fam, B):
-    """A handle of a copy of cfg on the family's layout, pinned to the family; iterate_kernel (and on
-    quad12's lane layouts solve_kernel) must name it, so a silent fallback cannot pass for coverage."""
-    from ilqr_iterative_tasks_amd import BatchedILQR
-    lid, options, name = families(plant)[fam]
-    cfg = cfg.copy()
-    cfg.layout = lid
-    solver = BatchedILQR(cfg)
-    for key, val in options.items():
-        solver.set_option(key, val)
-    solver.ensure_workspace(B)
-    got = solver.iterate_kernel(B)
-    assert got in name if isinstance(name, tuple) else got == name, (fam, got)
-    if name == "k_lane_iterate_rows":
-        assert solver.solve_kernel(B) == name
-    return solver, cfg
-
-
 def rel_cost(a, b):
     return np.abs(a - b) / np.maximum(np.abs(b), 1e-300)
-
-
-def assert_within(err, limit, what):
-    over = err > limit
-    worst = int(np.argmax(err / limit)) if len(err) else 0
-    assert not over.any(), (f"{what}: {int(over.sum())} problems over their bound, worst "
-                            f"{float((err / limit).max()):.2f} x (error {float(err[worst]):.3e}, "
-                            f"bound {float(limit[worst]):.3e}, entry {worst})")
 
 
 def finite(torch, *tensors):
