@@ -514,7 +514,7 @@ int64_t i2lqr_workspace_bytes(const i2lqr_handle* h, int64_t B) {
     using T = decltype(t);
     using Sys = decltype(sys);
     using L = LaneLaunch<T, Sys, false>;
-    return tiled ? LaneLaunch<T, Sys, true>::ws_bytes(L::shape(h), B) : L::ws_bytes(L::shape(h), B);
+    return tiled ? LaneLaunch<T, Sys, true>::ws_bytes(h, B) : L::ws_bytes(h, B);
   });
 }
 
@@ -567,6 +567,7 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
   else if (!strcmp(name, "state_buffers")) lane.opt_two_x = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "chunk_step")) lane.opt_chunk_step = v < 1 ? -1 : (v > 1024 ? 1024 : v);
   else if (!strcmp(name, "fused_compaction")) lane.opt_fuse = v < 0 ? -1 : (v != 0);
+  else if (!strcmp(name, "lane_model_chunks")) lane.opt_model_chunks = v == 1 ? 1 : -1;
   else if (!strcmp(name, "final_round")) lane.opt_final_round = v < 0 ? -1 : (v > 20 ? 20 : v);
   else if (!strcmp(name, "speculate")) col.opt_spec = v < 0 ? -1 : (v != 0);
   else if (!strcmp(name, "group_workspace")) col.opt_group_ws = v < 0 ? -1 : (v != 0);
@@ -670,8 +671,11 @@ static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit
   if (h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR) {
     if (h->cfg.system_id == I2LQR_SYS_QUAD12) return "k_lane_iterate_rows";
     // a form of "lane_models": what LaneLaunch::iterate launches from the same record
-    if (const LaneForm f = lane_model(h->model, h->lane_opt).form(); f != LANE_PLAIN)
-      return lane_kernel_name(f);
+    // ... "lane_model_chunks": with ", chunked" where its plan runs the solve as chunks
+    if (const LaneForm f = lane_model(h->model, h->lane_opt).form(); f != LANE_PLAIN) {
+      const auto chunks = [&](auto L) { return L.names_model_chunks(h, B, early_exit ? 1 : 0); };
+      return dispatch(h, chunks) == 1 ? lane_chunked_kernel_name(f) : lane_kernel_name(f);
+    }
     // the helper-wavefront form (both precisions, with or without stage weights): decided by the
     // launcher's own rules (LaneLaunch::names_pair)
     const auto pair = [&](auto L) { return L.names_pair(h, B, early_exit ? 1 : 0); };

@@ -160,6 +160,7 @@ template <class T, class Sys> struct Launch {
     return I2LQR_OK;
   }
   static int names_pair(const i2lqr_handle*, int64_t, int) { return 0; }
+  static int names_model_chunks(const i2lqr_handle*, int64_t, int) { return 0; }
   // io.B chains of k problems each in ONE launch (chain_plan)
   static int solve_chained(i2lqr_handle* h, const SolveIO& io, int k, hipStream_t s) {
     const ChainPlan plan = chain_plan(h->geo, h->fit, h->col, h->model.form(), registered_ws(h), io.B);

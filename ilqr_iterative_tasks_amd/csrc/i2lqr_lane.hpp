@@ -110,13 +110,17 @@ template <class T> struct LaneArgs {
 //                             ONE atomic add per wavefront (every chunk starts by rolling the states
 //                             out again, so a survivor carries its inputs and x_0 only).
 // The order of the slots is arbitrary (every problem is independent: results do not depend on it).
+// ob_rows: rows of obs a survivor carries, row for row (6; the model kernels: 6 K, i2lqr_lane_model.hpp).
+// Returns the survivor's slot in the next work set, -1 for a lane that packed nothing (the model
+// kernels carry their nominal's cost there; the other callers do not look at it).
 template <class T>
-__device__ __forceinline__ void lane_exit_compact(const LaneCompact<T>& cp, const int n, const int m,
+__device__ __forceinline__ int64_t lane_exit_compact(const LaneCompact<T>& cp, const int n, const int m,
                                                   const int N, const int64_t b, const int64_t Bs,
                                                   const unsigned bl, const T* X, const T* U,
                                                   const T* xt, const T* ob, const T* gK, const T* gk,
                                                   const T lamb, const T cost, const int iters,
-                                                  const int status, unsigned long long* trap) {
+                                                  const int status, unsigned long long* trap,
+                                                  const int ob_rows = 6) {
   (void)trap;
   const int rx = n * (N + 1), ru = m * N, rK = m * n * N;
   const LaneSet<T>& usr = cp.usr;
@@ -145,7 +149,7 @@ __device__ __forceinline__ void lane_exit_compact(const LaneCompact<T>& cp, cons
   const bool run = status == 0;
   const unsigned long long mask = __ballot(run);
   if (!run) {
-    if (cp.src_is_user || (status & kStatusDelivered)) return;  // in place / the tail kernel's
+    if (cp.src_is_user || (status & kStatusDelivered)) return -1;  // in place / the tail kernel's
     const int64_t o = cp.orig[b];
     move_rows(rx, [&](int r, T v) { usr.X[uaddr(rx, r, o)] = v; },
               [&](int r) { return X[(int64_t)r * Bs + bl]; });
@@ -161,10 +165,10 @@ __device__ __forceinline__ void lane_exit_compact(const LaneCompact<T>& cp, cons
     usr.cost[o] = cost;
     if (usr.iters) usr.iters[o] = iters;
     if (usr.status) usr.status[o] = status;
-    return;
+    return -1;
   }
   const LaneSet<T>& dst = cp.dst;
-  if (!dst.X) return;  // (cannot happen: the last chunk leaves no problem running)
+  if (!dst.X) return -1;  // (cannot happen: the last chunk leaves no problem running)
   // the running lanes of this wavefront claim consecutive slots with one atomic add
   const unsigned lane = threadIdx.x & 63;
   const int rank = __popcll(mask & ((1ull << lane) - 1ull));
@@ -180,12 +184,13 @@ __device__ __forceinline__ void lane_exit_compact(const LaneCompact<T>& cp, cons
   move_rows(n, [&](int r, T v) { dst.x_term[(int64_t)r * dst.B + j] = v; },
             [&](int r) { return xt[(int64_t)r * Bs + bl]; });
   if (ob)
-    move_rows(6, [&](int r, T v) { dst.obs[(int64_t)r * dst.B + j] = v; },
+    move_rows(ob_rows, [&](int r, T v) { dst.obs[(int64_t)r * dst.B + j] = v; },
               [&](int r) { return ob[(int64_t)r * Bs + bl]; });
   dst.lamb[j] = lamb;
   dst.iters[j] = iters;
   dst.status[j] = 0;  // RUNNING (a tail launch may finish it before the next chunk sees it)
   dst.orig[j] = cp.src_is_user ? (int32_t)b : cp.orig[b];
+  return j;
 }
 
 // State checkpointing (fp64, large batches: the kernel sits on the HBM roof).  Between the passes of

@@ -44,9 +44,17 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     a.X = w.X; a.U = w.U; a.x_term = w.x_term; a.lamb = w.lamb; a.obs = w.obs; a.cost = w.cost;
     a.K = w.K; a.k = w.k; a.iters = w.iters; a.status = w.status;
   }
+  // The workspace table of B problems on this handle: a model handle with "lane_model_chunks" 1 has
+  // work sets with all its records and, with the barrier cost, the penalty row - whatever the batch, so
+  // that the size does not jump at the chunked solve's threshold
+  static LaneWorkspace workspace(const i2lqr_handle* h, int64_t B) {
+    const LaneModel md = lane_model(h->model, h->lane_opt);
+    const bool sets = md.on() && h->lane.opt_model_chunks == 1;
+    return lane_workspace(shape(h), B, sets ? md.records : 1, sets && md.barrier_cost);
+  }
   // (the tiled layout's arrays are whole tiles of 64 problems)
-  static int64_t ws_bytes(const LaneShape& s, int64_t B) {
-    return lane_workspace(s, TILED ? (B + 63) / 64 * 64 : B).total;
+  static int64_t ws_bytes(const i2lqr_handle* h, int64_t B) {
+    return workspace(h, TILED ? (B + 63) / 64 * 64 : B).total;
   }
   static int prepare(i2lqr_handle* h) {
     h->lanes = 1;
@@ -62,7 +70,7 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     if (TILED && (B & 63))
       return fail(I2LQR_ERR_INVALID, "the batch-tiled layout needs a batch that is a multiple of "
                   "64 (got %lld)", (long long)B);
-    const int64_t need = ws_bytes(shape(h), B);
+    const int64_t need = ws_bytes(h, B);
     if (!h->ws || h->ws_bytes < need)
       return fail(I2LQR_ERR_INVALID, "workspace of %lld B registered, batch %lld needs %lld B "
                   "(i2lqr_workspace_bytes / i2lqr_set_workspace)", (long long)h->ws_bytes,
@@ -74,12 +82,13 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     int32_t* uiters;
     int32_t* ustatus;
     int32_t* count;  // [kMaxRounds]: the live count after each compaction round
+    T* pen[2];       // penalty rows of the work sets (a chunked model solve with the barrier cost), or null
   };
   // The arguments of a launch of B problems with the options `o`, its scratch carved from the
   // registered workspace (need_ws() has passed); cv: the chunked solve's work sets as well
   static LaneArgs<T> lane_args(const i2lqr_handle* h, int64_t B, const LaneOptions& o,
                                Carved* cv = nullptr) {
-    const LaneWorkspace w = lane_workspace(shape(h), B);
+    const LaneWorkspace w = workspace(h, B);
     char* const base = (char*)h->ws;
     LaneArgs<T> a;
     a.wsU = (T*)(base + w.wsU);
@@ -105,6 +114,7 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
                               (T*)(base + at.obs), (T*)(base + at.lamb), (T*)(base + at.cost),
                               a.wsK, a.wsk, (int32_t*)(base + at.iters),
                               (int32_t*)(base + at.status), (int32_t*)(base + at.orig), B};
+      cv->pen[q] = at.pen >= 0 ? (T*)(base + at.pen) : nullptr;
     }
     cv->uiters = (int32_t*)(base + w.uiters);
     cv->ustatus = (int32_t*)(base + w.ustatus);
@@ -170,7 +180,16 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
   // packed into a dense work set (k_lane_compact).  No host synchronisation: the live count stays
   // in device memory and surplus wavefronts exit at once.  Results are bit-identical to the plain
   // launch.
-  static int solve_compacting(i2lqr_handle* h, const SolveIO& io, hipStream_t s) {
+  // One routine for the plain kernels and the model kernels ("lane_model_chunks"): `o` are the
+  // options of its launches and chunk(TL, a, opt_pair, pen) launches one lane chunk with the
+  // arguments a - TL: std::true_type for chunk 0 of a batch-tiled handle (in place, in the caller's
+  // layout), std::false_type for the work sets; pen: the penalty rows the chunk reads and its exit
+  // fills.  model: lane chunks and the fused exit only - the tail kernels, k_lane_compact and the
+  // helper-wavefront form have no models, so "wave_tail", "final_round", "speculate" and
+  // "fused_compaction" have no effect.
+  template <class Chunk>
+  static int solve_compacting(i2lqr_handle* h, const SolveIO& io, hipStream_t s, const LaneOptions& o,
+                              const bool model, Chunk&& chunk) {
     const int64_t B = io.B;
     if (int rc = need_ws(h, B)) return rc;
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
@@ -178,7 +197,7 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     const LaneTune& tune = h->lane;
     const int N = h->cfg.N, max_iter = h->cfg.max_iter;
     Carved cv;
-    LaneArgs<T> a0 = lane_args(h, B, lane_options(h->geo, sh, tune, B, false), &cv);
+    LaneArgs<T> a0 = lane_args(h, B, o, &cv);
     LaneSet<T> usr = user_set(io);
     if (!io.iters) usr.iters = cv.uiters;
     if (!io.status) usr.status = cv.ustatus;
@@ -196,8 +215,8 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     // plants, stage weights) from 2048.
     bool spec_tail = false;
     if constexpr (m == 2 && n + m <= 8)
-      spec_tail = h->col.opt_spec != 0 && c.flags == 0 && group_spec_tail_supported(h->cfg);
-    const int wave_tail = tune.wave_tail < 0
+      spec_tail = !model && h->col.opt_spec != 0 && c.flags == 0 && group_spec_tail_supported(h->cfg);
+    const int wave_tail = model ? 0 : tune.wave_tail < 0
         ? (int)h->geo.scaled(spec_tail ? kAutoSpecTail : kAutoWaveTail) : tune.wave_tail;
     const ChunkSchedule plan = chunk_schedule(max_iter, tune.opt_first_chunk, tune.opt_chunk_step,
                                               tune.opt_final_round, wave_tail > 0, spec_tail);
@@ -209,7 +228,7 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     // terminated, one atomic add per wavefront, while the other wavefronts still iterate) — the
     // k_lane_compact launch between every two chunks and the final scatter pass are gone
     // ("fused_compaction" 0 brings them back: the A/B and the fallback).
-    const bool fused = tune.opt_fuse != 0;
+    const bool fused = model || tune.opt_fuse != 0;
     auto plan_exit = [&](LaneArgs<T>& a, bool src_user, const int32_t* orig, LaneSet<T>* dst,
                          int32_t* count_out) {
       std::memset(&a.cp, 0, sizeof(a.cp));
@@ -226,7 +245,7 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     set_io(a0, plan.round[0].len, 1, usr);
     a0.max_total = max_iter;
     plan_exit(a0, true, nullptr, plan.round[0].last ? nullptr : &cv.set[0], cv.count);
-    launch_iterate<TILED>(h->geo, c, sh, a0, B, s, tune.opt_pair);
+    chunk(std::integral_constant<bool, TILED>{}, a0, tune.opt_pair, LanePen<T>{nullptr, cv.pen[0]});
     const unsigned cgrid = (unsigned)((B + 255) / 256);
     bool src_user = true;
     const int32_t* count_in = nullptr;
@@ -283,13 +302,14 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
       ap.merge = tune.opt_merge >= 0 ? tune.opt_merge : 0;
       ap.reroll = tune.opt_reroll >= 0 ? tune.opt_reroll : 0;
       const unsigned pair_max = pair_max_grid(h->geo);
-      if (pair_built(sh, ap, tune.opt_pair) && tune.opt_pair < 0 && grid(B) > pair_max) {
+      const LanePen<T> pen{cv.pen[cur], cv.pen[cur ^ 1]};
+      if (!model && pair_built(sh, ap, tune.opt_pair) && tune.opt_pair < 0 && grid(B) > pair_max) {
         ap.count_hi = 64 * (int)pair_max;
         launch_pair<false>(h->geo, c, sh, ap, pair_max, s);
         a.count_lo = ap.count_hi;
-        launch_iterate<false>(h->geo, c, sh, a, B, s, 0);
+        chunk(std::false_type{}, a, 0, pen);
       } else {
-        launch_iterate<false>(h->geo, c, sh, a, B, s, tune.opt_pair);
+        chunk(std::false_type{}, a, tune.opt_pair, pen);
       }
       src = w;
       src_user = false;
@@ -306,43 +326,82 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     return I2LQR_OK;
   }
 
-  // i2lqr_iterate / i2lqr_solve with a model on: ONE launch of k_lane_iterate_model - with the barrier
-  // cost of k_lane_iterate_merit, with the line search of k_lane_iterate_ls (soft or barrier cost), same
-  // plan and same LDS - whatever the batch (a solve runs with early exit; "helper_wavefront",
-  // "checkpoint_states", "state_buffers" and i2lqr_set_compaction have no effect)
+  // One launch of the model kernel of `md` on the arguments a, in the layout TL: k_lane_iterate_model,
+  // with the barrier cost k_lane_iterate_merit, with the line search k_lane_iterate_ls (soft or barrier
+  // cost) - same plan, same LDS.  CHUNK selects k_lane_chunk_model / _merit / _ls instead: one chunk of
+  // the chunked solve, with LaneArgs' count / resume / max_total and the penalty rows `pen` in a
+  // LaneChunk argument.
+  template <bool TL, bool CHUNK>
+  static void launch_model(const i2lqr_handle* h, const Cfg& c, const LaneShape& sh,
+                           const LaneModelPlan& p, const LaneModel& md, LaneArgs<T> a, int64_t B,
+                           hipStream_t s, const LanePen<T> pen = LanePen<T>{nullptr, nullptr}) {
+    if constexpr (Sys::NBLK == 0) {
+      const BoxCfg<T, n> box = make_box_cfg<T, n>(h->model.box);
+      // one launch expression: the kernel's address and what follows c, a, md.records and box
+      const auto launch = [&](auto kernel, auto... tail) {
+        grow_lds(h->geo, kernel, sh, a, grid(B), p.model_bytes);
+        hipLaunchKernelGGL(kernel, dim3(grid(B)), dim3(64), lane_lds(sh, a) + p.model_bytes, s,
+                           c, a, md.records, box, tail...);
+      };
+      const T box_q1 = (T)h->model.box.q1;
+      with_weights(c.flags, [&](auto W) {
+        if constexpr (CHUNK) {
+          const LaneChunk<T> ck{a.count, a.resume, a.max_total, pen};
+          if (md.line_search > 1) {
+            // (lane_chunks_built(): the plan chunks no other line search)
+            if constexpr (kLaneLsChunkBuilt<T, Sys, W, true>)
+              launch(&k_lane_chunk_ls<T, Sys, W, TL, true>, box_q1, md.line_search, ck);
+          } else if (md.barrier_cost) {
+            launch(&k_lane_chunk_merit<T, Sys, W, TL>, box_q1, ck);
+          } else {
+            launch(&k_lane_chunk_model<T, Sys, W, TL>, ck);
+          }
+        } else {
+          if (md.line_search > 1 && md.barrier_cost)
+            launch(&k_lane_iterate_ls<T, Sys, W, TL, true>, box_q1, md.line_search);
+          else if (md.line_search > 1)
+            launch(&k_lane_iterate_ls<T, Sys, W, TL, false>, box_q1, md.line_search);
+          else if (md.barrier_cost)
+            launch(&k_lane_iterate_merit<T, Sys, W, TL>, box_q1);
+          else
+            launch(&k_lane_iterate_model<T, Sys, W, TL>);
+        }
+      });
+    }
+  }
+  // The plan of a model call of n_iters iterations, with or without early exit: the ONE place that
+  // says what a solve to termination is (early exit and max_iter iterations; the chunked solve is
+  // for nothing else, so any other call is planned with the option off)
+  static LaneModelPlan model_plan(const i2lqr_handle* h, const LaneModel& md, int64_t B,
+                                  int early_exit, int n_iters) {
+    LaneTune tune = h->lane;
+    if (!(early_exit && n_iters == h->cfg.max_iter)) tune.opt_model_chunks = -1;
+    return lane_model_plan(h->geo, shape(h), tune, md, B, early_exit != 0);
+  }
+  // i2lqr_iterate / i2lqr_solve with a model on: ONE launch whatever the batch (a solve runs with early
+  // exit; "helper_wavefront", "checkpoint_states", "state_buffers" have no effect, and neither has
+  // i2lqr_set_compaction) - unless "lane_model_chunks" is 1: then a solve to termination of a batch
+  // that chunked() takes runs as solve_compacting's lane chunks
   static int iterate_model(i2lqr_handle* h, const SolveIO& io, const LaneModel& md, hipStream_t s) {
     if constexpr (Sys::NBLK > 0) {
       return fail(I2LQR_ERR_UNSUPPORTED, "%s", lane_models_rows_text());
     } else {
       if (int rc = need_ws(h, io.B)) return rc;
       const LaneShape sh = shape(h);
-      const LaneModelPlan p = lane_model_plan(h->geo, sh, h->lane, md, io.B, io.early_exit != 0);
+      const LaneModelPlan p = model_plan(h, md, io.B, io.early_exit, io.n_iters);
       if (!p.fits)
         return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_models\": %d obstacle records take %zu B of LDS per "
                     "wavefront beside the %d B of k_0, a workgroup of this device gets %zu B",
                     md.records, p.model_bytes, sh.k0_bytes(), h->geo.default_dyn_lds);
       const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
+      if (p.chunked)
+        return solve_compacting(h, io, s, p.o, true, [&](auto tl, const LaneArgs<T>& a, int, LanePen<T> pen) {
+          launch_model<decltype(tl)::value, true>(h, c, sh, p, md, a, io.B, s, pen);
+        });
       LaneArgs<T> a = lane_args(h, io.B, p.o);
       set_io(a, io.n_iters, io.early_exit, user_set(io));
       a.max_total = io.n_iters;
-      const BoxCfg<T, n> box = make_box_cfg<T, n>(h->model.box);
-      // one launch expression: the kernel's address and what follows c, a, md.records and box
-      const auto launch = [&](auto kernel, auto... tail) {
-        grow_lds(h->geo, kernel, sh, a, grid(io.B), p.model_bytes);
-        hipLaunchKernelGGL(kernel, dim3(grid(io.B)), dim3(64), lane_lds(sh, a) + p.model_bytes, s,
-                           c, a, md.records, box, tail...);
-      };
-      const T box_q1 = (T)h->model.box.q1;
-      with_weights(c.flags, [&](auto W) {
-        if (md.line_search > 1 && md.barrier_cost)
-          launch(&k_lane_iterate_ls<T, Sys, W, TILED, true>, box_q1, md.line_search);
-        else if (md.line_search > 1)
-          launch(&k_lane_iterate_ls<T, Sys, W, TILED, false>, box_q1, md.line_search);
-        else if (md.barrier_cost)
-          launch(&k_lane_iterate_merit<T, Sys, W, TILED>, box_q1);
-        else
-          launch(&k_lane_iterate_model<T, Sys, W, TILED>);
-      });
+      launch_model<TILED, false>(h, c, sh, p, md, a, io.B, s);
       HIP_TRY(hipGetLastError());
       return I2LQR_OK;
     }
@@ -353,7 +412,13 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
       return iterate_model(h, io, md, s);
     const LaneShape sh = shape(h);
     const bool solve = io.early_exit && io.n_iters == h->cfg.max_iter;
-    if (solve && chunked(h->geo, sh, h->lane, io.B)) return solve_compacting(h, io, s);
+    if (solve && chunked(h->geo, sh, h->lane, io.B)) {
+      const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
+      return solve_compacting(h, io, s, lane_options(h->geo, sh, h->lane, io.B, false), false,
+                              [&](auto tl, const LaneArgs<T>& a, int opt_pair, LanePen<T>) {
+                                launch_iterate<decltype(tl)::value>(h->geo, c, sh, a, io.B, s, opt_pair);
+                              });
+    }
     if (int rc = need_ws(h, io.B)) return rc;
     const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
     LaneArgs<T> a = lane_args(h, io.B, lane_options(h->geo, sh, h->lane, io.B, io.early_exit != 0));
@@ -375,6 +440,12 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
     const LaneOptions o =
         lane_options(h->geo, sh, h->lane, B, early_exit && !chunked(h->geo, sh, h->lane, B));
     return use_pair(h->geo, sh, o, B, h->lane.opt_pair) ? 1 : 0;
+  }
+  // 1 if i2lqr_solve of B problems on this handle's model (LaneModel::on) runs as the chunked solve:
+  // the plan iterate_model() launches from
+  static int names_model_chunks(const i2lqr_handle* h, int64_t B, int early_exit) {
+    const LaneModel md = lane_model(h->model, h->lane_opt);
+    return md.on() && model_plan(h, md, B, early_exit, h->cfg.max_iter).chunked ? 1 : 0;
   }
   static int rollout(i2lqr_handle* h, int64_t B, void* X, void* U, const void* x_term, void* cost,
                      hipStream_t s) {

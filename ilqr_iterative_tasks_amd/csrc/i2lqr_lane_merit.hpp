@@ -106,6 +106,7 @@ template <class T, int n, int m> struct LaneMeritHook {
 
 // LaneArgs, K, the box and the dynamic LDS as k_lane_iterate_model takes them; box_q1: the box's q1.
 // a.cost returns J.
+// (k_lane_chunk_merit below is a copy of this loop with the chunk protocol: it must follow every change)
 template <class T, class Sys, bool HASQR, bool TILED>
 __global__ __launch_bounds__(64, (sizeof(T) == 4 ? I2LQR_F32_WAVES : I2LQR_F64_WAVES)) void
 k_lane_iterate_merit(const DevCfg<T, Sys::n, Sys::m> c, const LaneArgs<T> a, const int K,
@@ -224,9 +225,156 @@ k_lane_iterate_merit(const DevCfg<T, Sys::n, Sys::m> c, const LaneArgs<T> a, con
   if (a.status) a.status[b] = status;
 }
 
+// k_lane_chunk_merit: k_lane_iterate_merit as a chunk of the chunked, compacting solve, with the chunk
+// protocol of k_lane_chunk_model (i2lqr_lane_model.hpp; a copy of the kernel above for the same reason,
+// units i2lqr_lane_merit_chunk_f64.hip, _f32.hip).  c and P of a survivor's nominal go through the work
+// set's cost and penalty rows (ck.pen): the convergence test divides by c alone, and P inside the loop is
+// the forward pass's running sum, not nominal_penalty()'s.
+template <class T, class Sys, bool HASQR, bool TILED>
+__global__ __launch_bounds__(64, (sizeof(T) == 4 ? I2LQR_F32_WAVES : I2LQR_F64_WAVES)) void
+k_lane_chunk_merit(const DevCfg<T, Sys::n, Sys::m> c, const LaneArgs<T> a, const int K,
+                   const BoxCfg<T, Sys::n> box, const T box_q1, const LaneChunk<T> ck) {
+  constexpr int n = Sys::n, m = Sys::m;
+  const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  const int64_t live = ck.count ? (int64_t)*ck.count : a.B;
+  if (b >= live) return;
+  const int N = c.N;
+  const LaneView<TILED> v(a.B);
+  LaneWorker<T, Sys, HASQR, TILED> w(c, v.Bs, v.bl);
+  extern __shared__ __align__(16) unsigned char lane_smem[];
+  typedef __attribute__((address_space(3))) T lds_t;
+  w.lds = (lds_t*)lane_smem;
+  w.has_lds = true;
+  w.lds_steps = a.lds_steps;
+  using Hook = LaneModelHook<T, n>;
+  using Merit = LaneMeritHook<T, n, m>;
+  const Hook mdl{(lds_t*)lane_smem + (size_t)a.lds_steps * 64 * m * (n + 1) + 64 * m, K, box};
+  const T* gxt = v.rebase(a.x_term, n);
+  const T* gob = v.rebase(a.obs, 6 * K);
+  T xT[n], ob[6];
+#pragma unroll
+  for (int i = 0; i < n; i++) xT[i] = gxt[(int64_t)i * v.Bs + v.bl];
+  // a NULL obs disables every record (finite placeholders, as k_lane_iterate's)
+#pragma unroll
+  for (int q = 0; q < 6; q++)
+    ob[q] = gob ? gob[(int64_t)(q * K) * v.Bs + v.bl] : T(q == 5 ? -1 : 1);
+  for (int r = 1; r < K; r++) {
+    T rec[6];
+#pragma unroll
+    for (int q = 0; q < 6; q++)
+      rec[q] = gob ? gob[(int64_t)(q * K + r) * v.Bs + v.bl] : T(q == 5 ? -1 : 1);
+    rec[2] = T(1) / (rec[2] * rec[2]);
+    rec[3] = T(1) / (rec[3] * rec[3]);
+#pragma unroll
+    for (int q = 0; q < 6; q++) mdl.stage(r, q, rec[q]);
+  }
+  const Merit mh{mdl, ob, T(1) / (ob[2] * ob[2]), T(1) / (ob[3] * ob[3]), box_q1};
+  T lamb = a.lamb[b];
+  T* gK = v.rebase(a.K ? a.K : a.wsK, m * n * N);
+  T* gk = v.rebase(a.K ? a.k : a.wsk, m * N);
+  // (states in ONE buffer, inputs double-buffered per lane: see k_lane_iterate)
+  T* const X = v.rebase(a.X, n * (N + 1));
+  T* const U0 = v.rebase(a.U, m * N);
+  T *Uc = U0, *Un = v.rebase(a.wsU, m * N);
+  if (a.stagger > 0 && ((blockIdx.x >> 9) & 1)) {  // see k_lane_iterate_rows
+    for (int q = 0; q < a.stagger; q++) __builtin_amdgcn_s_sleep(127);
+  }
+  T cost = w.rollout(X, Uc, xT);  // c of the nominal: barrier-free
+  T pen;
+  // iterations of earlier chunks: the same for every problem of a chunk (no tail kernel between model
+  // chunks, and a survivor has used every iteration of every earlier chunk), so a scalar
+  const int it0 = ck.resume ? __builtin_amdgcn_readfirstlane(a.iters[b]) : 0;
+  if (ck.resume) {  // ... and c, P of the nominal they left
+    cost = a.cost[b];
+    pen = ck.pen.in[b];
+  } else {
+    pen = mh.nominal_penalty(w, X, Uc);
+  }
+  T J = cost + pen;
+  int it = 0, status = a.early_exit ? 2 : 0;
+  T J_ret = J;
+  // it < a.n_iters && it0 + it < max_total, as one wave-uniform bound
+  const int n_run = a.n_iters < ck.max_total - it0 ? a.n_iters : ck.max_total - it0;
+  while (it < n_run) {
+    // K_0 goes to HBM from the passes that can be this launch's last one for the problem
+    const bool k0_out = a.early_exit || it + 1 >= n_run;
+    w.template backward<true, false, 0, Hook>(X, Uc, xT, ob, lamb, gK, gk, k0_out, nullptr, mdl);
+    constexpr int D = LaneWorker<T, Sys, HASQR, TILED>::DEEP ? 2 : 1;  // (forward's own default)
+    T cost_new, pen_new;
+    if (a.defer) {
+      cost_new = a.reroll
+          ? w.template forward<true, false, D, Merit>(X, Uc, gK, gk, X, Un, xT, mh, &pen_new)
+          : w.template forward<false, false, D, Merit>(X, Uc, gK, gk, X, Un, xT, mh, &pen_new);
+    } else {
+      cost_new = a.reroll
+          ? w.template forward<true, true, D, Merit>(X, Uc, gK, gk, X, Un, xT, mh, &pen_new)
+          : w.template forward<false, true, D, Merit>(X, Uc, gK, gk, X, Un, xT, mh, &pen_new);
+    }
+    it++;
+    // accept / reject on the merit, with the lamb schedule of control/iterative_ilqr.py:74-84
+    const T J_new = cost_new + pen_new;
+    const bool accepted = t_isfinite(J_new) && J_new < J;
+    // X must hold the states of each lane's CURRENT inputs (see k_lane_iterate)
+    if (a.defer && a.merge) {
+      if (__all(accepted)) {
+        T* tp = Uc; Uc = Un; Un = tp;
+        w.restore_states(X, Uc);
+      } else if (__any(accepted)) {
+        w.merge_and_restore(X, Uc, Un, accepted);
+      }
+    } else {
+      if (accepted) {
+        T* tp = Uc; Uc = Un; Un = tp;
+      }
+      if (__any(a.defer ? accepted : !accepted)) w.restore_states(X, Uc);
+    }
+    if (accepted) {
+      lamb /= c.lamb_factor;
+      const bool conv = t_abs((J_new - J) / cost) < c.eps;
+      J_ret = J_new;
+      // next nominal: stage terms are measured to xtarget, not x_terminal, when Q != 0
+      cost = HASQR ? w.nominal_cost(X, Uc, xT) : cost_new;
+      pen = pen_new;
+      J = cost + pen;
+      if (conv) {
+        if (a.early_exit) { status = 1; break; }
+        if (status == 0) status = 1;
+      }
+    } else {
+      lamb *= c.lamb_factor;
+      J_ret = J;
+      if (lamb > c.max_lamb) {
+        if (a.early_exit) { status = 3; break; }
+        if (status == 0) status = 3;
+      }
+    }
+  }
+  // a chunk that ran out before the problem terminated: RUNNING unless the iteration cap is hit
+  if (a.early_exit && status == 2 && it0 + it < ck.max_total) status = 0;
+  if (!t_isfinite(J_ret) && (status != 0 || !a.early_exit)) status = 4;
+  w.flush_gains(gK, gk);
+  if (Uc != U0) {  // the accepted inputs sit in the workspace: copy them out
+    for (int e = 0; e < m * N; e++) U0[(int64_t)e * v.Bs + v.bl] = Uc[(int64_t)e * v.Bs + v.bl];
+  }
+  a.lamb[b] = lamb;
+  a.cost[b] = J_ret;
+  if (a.iters) a.iters[b] = it0 + it;
+  if (a.status) a.status[b] = status;
+  if (a.cp.on) {
+    const int64_t j = lane_exit_compact(a.cp, n, m, N, b, v.Bs, v.bl, X, U0, gxt, gob, gK, gk, lamb,
+                                        J_ret, it0 + it, status, c.trap, 6 * K);
+    if (j >= 0) {
+      a.cp.dst.cost[j] = cost;
+      ck.pen.out[j] = pen;
+    }
+  }
+}
+
 // The sixteen instantiations (I2LQR_LANE_OPT_KERNELS, i2lqr_lane_model.hpp): `extern template` for
 // the launcher, the instantiations in the two units
 I2LQR_LANE_OPT_KERNELS(extern template __global__, k_lane_iterate_merit, I2LQR_LANE_TAIL_MERIT, double)
 I2LQR_LANE_OPT_KERNELS(extern template __global__, k_lane_iterate_merit, I2LQR_LANE_TAIL_MERIT, float)
+I2LQR_LANE_OPT_KERNELS(extern template __global__, k_lane_chunk_merit, I2LQR_LANE_TAIL_CHUNK_MERIT, double)
+I2LQR_LANE_OPT_KERNELS(extern template __global__, k_lane_chunk_merit, I2LQR_LANE_TAIL_CHUNK_MERIT, float)
 
 }  // namespace i2lqr

@@ -58,6 +58,17 @@ inline const char* lane_kernel_name(LaneForm f) {
   }
 }
 
+// ... and i2lqr_solve_kernel where the solve runs as chunks with compaction ("lane_model_chunks")
+inline const char* lane_chunked_kernel_name(LaneForm f) {
+  switch (f) {
+    case LANE_MERIT: return "k_lane_iterate (barrier cost), chunked";
+    case LANE_BOX: return "k_lane_iterate (state box), chunked";
+    case LANE_OBS: return "k_lane_iterate (several obstacles), chunked";
+    case LANE_LS: return "k_lane_iterate (line search), chunked";
+    default: return "k_lane_iterate, chunked";
+  }
+}
+
 // An answer of the rules below: I2LQR_OK, or the error code and the text of i2lqr_last_error
 struct LaneRefusal {
   int code = I2LQR_OK;

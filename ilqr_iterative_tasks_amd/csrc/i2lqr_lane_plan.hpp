@@ -33,6 +33,7 @@ struct LaneTune {
   int opt_fuse = -1;  // chunked solve: compaction folded into the chunk kernels' exit (round 6); 0: k_lane_compact launches; automatic: on
   int opt_final_round = -1;  // chunked solve: the round whose tail kernel takes every survivor and ends the schedule; 0: never
   int opt_first_chunk = -1;  // chunked solve: pinned length of the first chunk, no extension chunks (a hand-tuned schedule to measure the data-driven one against)
+  int opt_model_chunks = -1;  // "lane_model_chunks" 1: i2lqr_solve of a model handle (LaneModel::on) runs as the chunked solve where chunked() holds; automatic: off
 };
 
 // What a launcher instantiation and the handle's configuration fix
@@ -176,12 +177,24 @@ inline LaneOptions lane_options(const DeviceGeometry& g, const LaneShape& s, con
 inline size_t lane_model_bytes(const LaneShape& s, const LaneModel& md) {
   return md.records > 1 ? (size_t)64 * 6 * (size_t)(md.records - 1) * (size_t)s.word : 0;
 }
-// A model launch: k_lane_iterate's one-wavefront form, states not checkpointed, i2lqr_solve as ONE
-// launch with early exit whatever the batch (k_lane_compact and the tail kernels have no models).
+// A model launch: k_lane_iterate's one-wavefront form, states not checkpointed.  i2lqr_solve is ONE
+// launch with early exit whatever the batch, unless "lane_model_chunks" is 1: then it is the chunked
+// solve from the batch chunked() gives, with lane chunks and the fused exit only (k_lane_compact and
+// the tail kernels have no models) and the options of a launch that is not a single-launch solve.
 // The records take the place of LDS-resident gain steps.
+// Which forms have chunk kernels.  k_lane_chunk_model and k_lane_chunk_merit: all.  k_lane_chunk_ls
+// (the line search): with the barrier cost only, and not bicycle6 in fp32 with stage weights - the
+// other instantiations do not compile without scratch (the soft ones keep a spilled scalar tuple's
+// frame, fp32 bicycle6 with weights spills vector registers inside the loop: DESIGN.md 3.5), so they
+// are not built and such a solve stays ONE launch.  The one rule: the kernel list
+// (i2lqr_lane_ls.hpp), the launcher and the plan below all read it.
+constexpr bool lane_chunks_built(int word, int n, bool weights, int line_search, bool barrier_cost) {
+  return line_search <= 1 || (barrier_cost && !(word == 4 && n > 4 && weights));
+}
 struct LaneModelPlan {
   LaneOptions o;
-  bool pair, chunked;  // always false: the helper-wavefront form and the chunked solve have no models
+  bool pair;     // always false: the helper-wavefront form has no models
+  bool chunked;  // a solve to termination with "lane_model_chunks" 1, chunked() and lane_chunks_built()
   size_t model_bytes;
   size_t lds;   // dynamic LDS the launch asks for before grown_lds_steps(): gain steps + k_0 + records
   bool fits;    // k_0 and the records fit the dynamic LDS a workgroup gets without asking for more
@@ -192,13 +205,14 @@ inline LaneModelPlan lane_model_plan(const DeviceGeometry& g, const LaneShape& s
   LaneTune tm = t;
   tm.opt_ckpt = 0;
   tm.opt_pair = 0;
-  p.o = lane_options(g, s, tm, B, solve);
+  p.chunked = solve && t.opt_model_chunks == 1 && chunked(g, s, t, B) &&
+              lane_chunks_built(s.word, s.n, s.weights, md.line_search, md.barrier_cost);
+  p.o = lane_options(g, s, tm, B, solve && !p.chunked);
   p.model_bytes = lane_model_bytes(s, md);
   const long room = (long)g.lds_per_simd_wave() - (long)s.k0_bytes() - (long)p.model_bytes;
   const int steps = room > 0 ? (int)(room / s.step_bytes()) : 0;
   if (p.o.lds_steps > steps) p.o.lds_steps = steps;
   p.pair = use_pair(g, s, p.o, B, tm.opt_pair);
-  p.chunked = false;
   p.lds = lane_lds(s, p.o) + p.model_bytes;
   p.fits = (size_t)s.k0_bytes() + p.model_bytes <= g.default_dyn_lds;
   return p;
@@ -208,8 +222,11 @@ inline LaneModelPlan lane_model_plan(const DeviceGeometry& g, const LaneShape& s
 // scratch + the second state buffer of the helper-wavefront form (every call), and for the chunked
 // solve two compacted work sets, scratch iters / status and one counter per round.  ONE table:
 // i2lqr_workspace_bytes returns `total`, the launcher carves base + offset.
+// records, pen: the work sets of a chunked MODEL solve ("lane_model_chunks") hold 6 records rows of
+// obs (row q records + r, as the caller's array) and, with the barrier cost, a row for the penalty of
+// the nominal behind the cost row; the defaults are the table of every other handle.
 struct LaneWorkspace {
-  struct Set { int64_t X, U, x_term, obs, lamb, cost, iters, status, orig; };
+  struct Set { int64_t X, U, x_term, obs, lamb, cost, iters, status, orig, pen = -1; };
   int64_t wsU, wsK, wsk;
   // second state buffer of the helper-wavefront form (rows of its own behind the gains scratch
   // since round 6 — the chunks' exits pack survivors into the work set the chunk does not run on,
@@ -220,7 +237,7 @@ struct LaneWorkspace {
   int64_t count;  // [kMaxRounds]: the live count after each compaction round
   int64_t total;
 };
-inline LaneWorkspace lane_workspace(const LaneShape& s, int64_t B) {
+inline LaneWorkspace lane_workspace(const LaneShape& s, int64_t B, int records = 1, bool pen = false) {
   LaneWorkspace w;
   int64_t p = 0;
   const auto take = [&p](int64_t bytes) { const int64_t at = p; p += bytes; return at; };
@@ -233,9 +250,10 @@ inline LaneWorkspace lane_workspace(const LaneShape& s, int64_t B) {
     q.X = take(row * (n * (N + 1)));
     q.U = take(row * (m * N));
     q.x_term = take(row * n);
-    q.obs = take(row * 6);
+    q.obs = take(row * 6 * records);
     q.lamb = take(row);
     q.cost = take(row);
+    if (pen) q.pen = take(row);
   }
   // the int32 arrays start on the next multiple of 16 (the base is 16-byte aligned); 16 bytes are
   // set aside for that, and what the alignment does not use of them is left behind the counters

@@ -176,7 +176,19 @@ class BatchedILQR:
         through the accept / reject step the solver has, soft or "lane_barrier_cost"'s; composes
         with "obstacles", set_state_box() and "lane_barrier_cost", and one record without a box is
         valid; every iterate() / solve() of the solver, a single launch; 0 / 1 off; "lane_models"
-        cannot be switched off while it is on; "line_search" itself stays refused on these layouts).
+        cannot be switched off while it is on; "line_search" itself stays refused on these layouts),
+        "lane_model_chunks" (a scheduling option, accepted on every solver and in any order; 1: solve()
+        of a lane solver with a model on - records, a box, "lane_barrier_cost", "lane_line_search" -
+        runs as the chunked, compacting solve from the batch set_compaction() gives (automatic: 4096
+        problems), on the plain solve's schedule ("first_chunk", "chunk_step"), bit-identical to the
+        single launch; solve_kernel(B) then ends in ", chunked".  Lane chunks only: no tail kernel, so
+        "wave_tail", "final_round" and "speculate" have no effect with a model on; no helper-wavefront
+        chunk, no checkpointed states; always the fused exit, so "fused_compaction" 0 has no effect with
+        a model on; quad12 stays refused; a line search is chunked with "lane_barrier_cost" only, and
+        not bicycle6 in fp32 with stage weights (such a solve stays a single launch).  The workspace grows by the records' rows of the two work
+        sets: ensure_workspace() asks again before every call.  iterate(), iterate_pick() and batches
+        under the threshold are unaffected; 0 / -1 off, the default: a model solve() is a single
+        launch).
         All but "wave_tail", "group_lanes", "line_search", "obstacles", "barrier_cost",
         "lane_barrier_cost" and "lane_line_search" leave the results bit-identical."""
         self._check(self.lib.i2lqr_set_option(self._handle, name.encode(), int(value)))

@@ -396,9 +396,10 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     While a model is on, i2lqr_iterate and i2lqr_solve run k_lane_iterate_model:
  *                     one problem per lane, one wavefront per workgroup; the records beyond the first
  *                     are staged in LDS (64 * 6 * (K - 1) words per wavefront) in place of
- *                     LDS-resident gain steps.  i2lqr_solve is then always a SINGLE launch with early
- *                     exit: i2lqr_set_compaction is ignored (the compaction and the tail kernels have
- *                     no models), as are "helper_wavefront", "checkpoint_states" and
+ *                     LDS-resident gain steps.  i2lqr_solve is then a SINGLE launch with early
+ *                     exit unless "lane_model_chunks" (below) is 1: i2lqr_set_compaction is ignored
+ *                     (k_lane_compact and the tail kernels have no models), as are
+ *                     "helper_wavefront", "checkpoint_states" and
  *                     "state_buffers"; "defer_states", "reroll_nominal", "merge_inputs",
  *                     "lds_gain_steps" and "stagger" apply and preserve the results bit for bit.
  *                     i2lqr_iterate_pick takes its unfused form; i2lqr_backward answers
@@ -519,6 +520,36 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     "lane_models" is not 1, quad12.  "lane_models" 0 while this option is on is
  *                     I2LQR_ERR_INVALID: switch "lane_line_search" off first.  "line_search" itself
  *                     stays I2LQR_ERR_UNSUPPORTED on these layouts.
+ *   "lane_model_chunks"  a scheduling option of the batch-minor / batch-tiled layouts, accepted on every
+ *                     handle and in any order with the others; it refuses nothing.  1: i2lqr_solve (a
+ *                     call with early exit and max_iter iterations) of a handle with a model on -
+ *                     records or a box of "lane_models", "lane_barrier_cost", "lane_line_search" -
+ *                     runs as the chunked, compacting solve from the batch i2lqr_set_compaction gives
+ *                     (automatic: 4096 problems, max_iter > 16), on the schedule of the plain solve
+ *                     ("first_chunk", "chunk_step"): a problem that has terminated stops occupying a
+ *                     lane.  The chunks are k_lane_chunk_model / _merit / _ls (the loops of
+ *                     k_lane_iterate_model / _merit / _ls with the chunk protocol), chunk 0 in
+ *                     place in the handle's layout, the others on batch-minor work sets that hold all
+ *                     6 K rows of a survivor's records and, with the barrier cost, the penalty of its
+ *                     nominal beside the cost.  Bit-identical to the single launch.  This first form
+ *                     has lane chunks only: no tail kernel (the one-problem-per-wavefront model kernels
+ *                     sum in another order), so "wave_tail", "final_round" and "speculate" have no
+ *                     effect with a model on; no helper-wavefront chunk and no checkpointed states;
+ *                     the compaction is always the fused exit - "fused_compaction" 0 has no effect
+ *                     with a model on, k_lane_compact has no models; quad12 stays refused as under
+ *                     "lane_models".  A line search ("lane_line_search" 2 / 4 / 8) has chunk kernels
+ *                     with the barrier cost only, and not for bicycle6 in fp32 with stage weights:
+ *                     every other line-search solve stays ONE launch with the option on (and
+ *                     i2lqr_solve_kernel says so).  The chunks take the scheduling options of a launch that is not
+ *                     a single-launch solve ("defer_states", "reroll_nominal", ... automatic as for
+ *                     i2lqr_iterate).  While it is 1 and a model is on, i2lqr_workspace_bytes is larger
+ *                     (2 (6 (K - 1) + barrier cost) rows of B words), whatever the batch; a smaller
+ *                     registered workspace is I2LQR_ERR_INVALID with the size needed.
+ *                     i2lqr_solve_kernel reports the form's name with ", chunked" appended exactly where
+ *                     the chunks run.  i2lqr_iterate with a fixed count, i2lqr_iterate_pick, batches
+ *                     under the threshold and handles without a model are unaffected.  -1, 0 (the
+ *                     default and the automatic choice): off - a model solve is ONE launch, as
+ *                     written under "lane_models".
  *   "stagger"         lane layouts (k_lane_iterate_rows, k_lane_iterate): every second half-thousand
  *                     of workgroups starts value x ~8000 cycles late, so that half of the
  *                     wavefronts stream their gains (forward pass) while the other half computes
@@ -574,7 +605,9 @@ int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, dou
  * Host only; "" for a NULL handle. */
 const char* i2lqr_iterate_kernel(const i2lqr_handle* h, int64_t B);
 /* The same for i2lqr_solve / early-exit calls (the dominant kernel; the chunked solves of the lane
- * layouts also launch a tail kernel, and k_lane_compact with "fused_compaction" 0). */
+ * layouts also launch a tail kernel, and k_lane_compact with "fused_compaction" 0).  A lane form's
+ * name ends in ", chunked" - "k_lane_iterate (state box), chunked" - exactly where "lane_model_chunks"
+ * runs the solve as chunks with compaction. */
 const char* i2lqr_solve_kernel(const i2lqr_handle* h, int64_t B);
 
 /*
