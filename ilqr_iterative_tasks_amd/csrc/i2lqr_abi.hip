@@ -607,6 +607,10 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value) {
     if (int rc = lane_ask(h, LANE_ASK_MODELS, v)) return rc;
     h->lane_opt.models = v == 1;
   }
+  else if (!strcmp(name, "lane_rows_models")) {
+    if (int rc = lane_ask(h, LANE_ASK_ROWS_MODELS, v)) return rc;
+    h->lane_opt.rows_models = v == 1;
+  }
   else if (!strcmp(name, "barrier_cost")) {
     if (v != -1 && v != 0 && v != 1)
       return fail(I2LQR_ERR_INVALID, "\"barrier_cost\" is 1 (on), or -1 / 0 (off)");
@@ -669,7 +673,10 @@ int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, dou
 static const char* kernel_name(const i2lqr_handle* h, int64_t B, bool early_exit) {
   if (!h) return "";
   if (h->cfg.layout != I2LQR_LAYOUT_PROBLEM_MAJOR) {
-    if (h->cfg.system_id == I2LQR_SYS_QUAD12) return "k_lane_iterate_rows";
+    // ("lane_rows_models": k_lane_iterate_rows_model with records or a box, from the same record)
+    if (h->cfg.system_id == I2LQR_SYS_QUAD12)
+      return lane_rows_kernel_name(h->lane_opt.rows_models ? lane_model(h->model, h->lane_opt).form()
+                                                           : LANE_PLAIN);
     // a form of "lane_models": what LaneLaunch::iterate launches from the same record
     // ... "lane_model_chunks": with ", chunked" where its plan runs the solve as chunks
     if (const LaneForm f = lane_model(h->model, h->lane_opt).form(); f != LANE_PLAIN) {

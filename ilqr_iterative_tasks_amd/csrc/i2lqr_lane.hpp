@@ -1255,10 +1255,16 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
   // sin / cos out of range, Quu not positive definite), in which case the caller repeats the pass
   // with GENERAL = true (same protocol as the other kernel families: the general forms' cold code
   // — library sincos, Jacobi sweeps — stays out of the loop the register allocator has to fit).
-  template <bool FASTBAR, bool GENERAL = true>
+  // MODEL (k_lane_iterate_rows_model, i2lqr_lane_rows_model.hpp): obstacle records 1 ... K - 1 join the
+  // five words of record 0 in record order where the step forms them (and in the terminal block), so
+  // they are parked and added with them; the state box's d1 / d2 of a state go on [Vxx | Vx] at the
+  // top of the step whose evaluation state it is - step t holds x_{t+1} in full (xe) there, and the
+  // value function of step t + 1 (of the terminal block at t = N - 1) is complete but for them: the
+  // order DESIGN.md 3.1 fixes, constant terms, obstacle terms, box.  No new word is parked.
+  template <bool FASTBAR, bool GENERAL = true, class MODEL = NoModel>
   __device__ __forceinline__ bool backward_blocked(const T* X, const T* U, const T (&xT)[n],
                                                    const T (&ob)[6], T lamb, T* gK, T* gk,
-                                                   T* lds_gains) const {
+                                                   T* lds_gains, const MODEL& mdl = MODEL()) const {
     bool bad = false;
     // the step's [Kc | k] in this wavefront's LDS slice (kGainWords words), typed as LDS (ds_*
     // with immediate offsets).  Stores index with the lane, loads with a copy of it whose origin
@@ -1294,6 +1300,7 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
         }
         vx[i] = acc;
       }
+      if constexpr (MODEL::kOn) mdl.more_obstacles(*this, ob[5] >= T(0), xN[0], xN[1], N, o);
       V[0][0] += o[2]; V[0][1] += o[3]; V[1][1] += o[4];
       vx[0] += o[0]; vx[1] += o[1];
     }
@@ -1312,6 +1319,8 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
     for (int t = N - 1; t >= 0; t--) {
       T jv[NV], o[5], tr[NT];
       STAMP_END(6);
+      // the box terms of x_{t+1} close [Vxx | Vx] of step t + 1 (of the terminal block at t = N - 1)
+      if constexpr (MODEL::kOn) mdl.box_add(xe, V, vx);
       if constexpr (GENERAL) Sys::trig(xe, tr);
       else Sys::trig_s(xe, tr, &bad);
       {
@@ -1352,6 +1361,7 @@ template <class T, class Sys, bool HASQR, bool TILED> struct LaneWorker {
       } else {
         obstacle_sel<GENERAL>(ob, ob_pa, ob_pb, xp[0], xp[1], t, o);
       }
+      if constexpr (MODEL::kOn) mdl.more_obstacles(*this, ob[5] >= T(0), xp[0], xp[1], t, o);
 #pragma unroll
       for (int a = 0; a < m; a++) {
         T e_hi, e_lo;

@@ -18,6 +18,7 @@
 #include "i2lqr_lane_merit.hpp"
 #include "i2lqr_lane_model.hpp"
 #include "i2lqr_lane_plan.hpp"
+#include "i2lqr_lane_rows_model.hpp"
 
 // the launches below are recorded by the dry-run build (empty unless -DI2LQR_DRY_RUN: the ASan build)
 #define I2LQR_DRY_RUN_LANE 1
@@ -384,7 +385,33 @@ template <class T, class Sys, bool TILED> struct LaneLaunch {
   // that chunked() takes runs as solve_compacting's lane chunks
   static int iterate_model(i2lqr_handle* h, const SolveIO& io, const LaneModel& md, hipStream_t s) {
     if constexpr (Sys::NBLK > 0) {
-      return fail(I2LQR_ERR_UNSUPPORTED, "%s", lane_models_rows_text());
+      // "lane_rows_models" 1: k_lane_iterate_rows_model, ONE launch ("lane_model_chunks" has no effect)
+      if (!h->lane_opt.rows_models) return fail(I2LQR_ERR_UNSUPPORTED, "%s", lane_models_rows_text());
+      if (md.barrier_cost || md.line_search > 1)  // (lane_refusal never lets a quad12 handle hold them)
+        return fail(I2LQR_ERR_UNSUPPORTED, "%s", lane_models_rows_text());
+      if (has_stage_weights(h->cfg))
+        return fail(I2LQR_ERR_UNSUPPORTED, "%s", lane_rows_models_weights_text());
+      if (int rc = need_ws(h, io.B)) return rc;
+      const LaneShape sh = shape(h);
+      using LW = LaneWorker<T, Sys, false, TILED>;
+      static_assert(LW::kGainWords == lane_rows_gain_words(n, m, NT, Sys::NJX),
+                    "lane_rows_model_plan budgets the row-block pass's LDS slice");
+      const LaneRowsModelPlan p = lane_rows_model_plan(h->geo, sh, h->lane, md, io.B, LW::kGainWords);
+      if (!p.fits)
+        return fail(I2LQR_ERR_UNSUPPORTED, "\"lane_rows_models\": k_lane_iterate_rows_model takes %zu B "
+                    "of LDS per wavefront, a quarter of this device's compute unit is %zu B",
+                    p.lds_bytes, h->geo.lds_per_cu / 4);
+      const Cfg c = make_dev_cfg<T, n, m>(h->cfg);
+      LaneOptions o = lane_options(h->geo, sh, h->lane, io.B, io.early_exit != 0);
+      o.stagger = p.stagger;
+      LaneArgs<T> a = lane_args(h, io.B, o);
+      set_io(a, io.n_iters, io.early_exit, user_set(io));
+      a.max_total = io.n_iters;
+      const BoxCfg<T, n> box = make_box_cfg<T, n>(h->model.box);
+      hipLaunchKernelGGL((k_lane_iterate_rows_model<T, Sys, false, TILED>), dim3(p.grid), dim3(64), 0,
+                         s, c, a, md.records, box);
+      HIP_TRY(hipGetLastError());
+      return I2LQR_OK;
     } else {
       if (int rc = need_ws(h, io.B)) return rc;
       const LaneShape sh = shape(h);

@@ -17,6 +17,9 @@ struct LaneOptIn {
   bool models = false;  // "lane_models" 1: the handle accepts model.obs and model.box; never set on a problem-major handle
   bool barrier_cost = false;  // "lane_barrier_cost" 1; only ever set while models is
   int line_search = 0;  // "lane_line_search" 2 / 4 / 8; 0: off; only ever set while models is
+  // "lane_rows_models" 1: a handle of a row-block plant (quad12) accepts model.obs and model.box as
+  // well, for k_lane_iterate_rows_model; only ever set while models is, never on a bicycle handle
+  bool rows_models = false;
 };
 
 // The forms in precedence order, as WaveForm ranks them: the barrier cost above the box, the box above
@@ -58,6 +61,17 @@ inline const char* lane_kernel_name(LaneForm f) {
   }
 }
 
+// ... of a row-block plant (quad12) with "lane_rows_models" 1: k_lane_iterate_rows_model
+// (i2lqr_lane_rows_model.hpp) has the records and the box; a handle with neither runs and reports
+// k_lane_iterate_rows
+inline const char* lane_rows_kernel_name(LaneForm f) {
+  switch (f) {
+    case LANE_BOX: return "k_lane_iterate_rows (state box)";
+    case LANE_OBS: return "k_lane_iterate_rows (several obstacles)";
+    default: return "k_lane_iterate_rows";
+  }
+}
+
 // ... and i2lqr_solve_kernel where the solve runs as chunks with compaction ("lane_model_chunks")
 inline const char* lane_chunked_kernel_name(LaneForm f) {
   switch (f) {
@@ -89,10 +103,17 @@ inline LaneRefusal refuse_layout(const char* what) {
                      "one-problem-per-wavefront kernel)", what);
 }
 // LaneLaunch::iterate_model of a row-block plant (quad12): the same rule as lane_refusal's, met by a
-// launch instead of a request
+// launch instead of a request (a handle without "lane_rows_models" 1)
 inline const char* lane_models_rows_text() {
   return "\"lane_models\" is built for the bicycles' one-problem-per-lane kernel, not for the "
          "row-block kernel of this plant (k_lane_iterate_rows): use the problem-major layout";
+}
+
+// ... and of a quad12 handle with "lane_rows_models" 1, a model and stage weights: that instantiation of
+// k_lane_iterate_rows_model is not built (it compiles with more scratch than k_lane_iterate_rows's)
+inline const char* lane_rows_models_weights_text() {
+  return "\"lane_rows_models\": k_lane_iterate_rows_model is built for Q = R = 0 (with stage weights "
+         "the records and the box run on the problem-major layout)";
 }
 
 // What i2lqr_set_option / i2lqr_set_state_box may be asked that concerns the lane forms
@@ -103,6 +124,7 @@ enum LaneAsk {
   LANE_ASK_BARRIER_COST,  // "lane_barrier_cost" v
   LANE_ASK_LINE_SEARCH,   // "lane_line_search" v
   WAVE_ASK_BARRIER_COST,  // "barrier_cost" v: a lane handle is pointed at "lane_barrier_cost"
+  LANE_ASK_ROWS_MODELS,   // "lane_rows_models" v
 };
 // `what` as a refusal names it, and for the two lane options their problem-major counterpart
 inline const char* lane_ask_phrase(LaneAsk what) {
@@ -112,6 +134,7 @@ inline const char* lane_ask_phrase(LaneAsk what) {
     case LANE_ASK_MODELS: return "\"lane_models\"";
     case LANE_ASK_BARRIER_COST: return "\"lane_barrier_cost\"";
     case LANE_ASK_LINE_SEARCH: return "\"lane_line_search\"";
+    case LANE_ASK_ROWS_MODELS: return "\"lane_rows_models\"";
     default: return wave_phrase(WAVE_MERIT);
   }
 }
@@ -123,7 +146,9 @@ inline const char* lane_ask_counterpart(LaneAsk what) {
 // whose lane kernel is k_lane_iterate_rows) that holds `model` and `opt`?  The one place that knows:
 // the values an option takes; that the lane options belong to the lane layouts and "barrier_cost" to
 // the other; that records, the box and the two lane options need "lane_models" 1 and the bicycles;
-// that "lane_models" stays while any of them is on.  Off-values are accepted everywhere.
+// that "lane_models" stays while any of them is on; that "lane_rows_models" opens records and the box
+// (and nothing else) to quad12, needs "lane_models" 1 and stays while either is on.  Off-values are
+// accepted everywhere.
 inline LaneRefusal lane_refusal(LaneAsk what, int v, bool problem_major, bool rows,
                                 const WaveModel& model, const LaneOptIn& opt) {
   const char* const name = lane_ask_phrase(what);
@@ -131,7 +156,8 @@ inline LaneRefusal lane_refusal(LaneAsk what, int v, bool problem_major, bool ro
   const bool lane_option = what == LANE_ASK_BARRIER_COST || what == LANE_ASK_LINE_SEARCH;
   if (steps && v != -1 && v != 0 && v != 1 && v != 2 && v != 4 && v != 8)
     return lane_refuse(I2LQR_ERR_INVALID, "%s is 2, 4 or 8 step sizes, or -1 / 0 / 1 (off)", name);
-  if ((what == LANE_ASK_MODELS || what == LANE_ASK_BARRIER_COST) && v != -1 && v != 0 && v != 1)
+  if ((what == LANE_ASK_MODELS || what == LANE_ASK_BARRIER_COST || what == LANE_ASK_ROWS_MODELS) &&
+      v != -1 && v != 0 && v != 1)
     return lane_refuse(I2LQR_ERR_INVALID, "%s is 1 (on), or -1 / 0 (off)", name);
   const bool on = steps || what == LANE_ASK_OBSTACLES ? v > 1 : v == 1;
   if (what == LANE_ASK_MODELS) {
@@ -143,7 +169,29 @@ inline LaneRefusal lane_refusal(LaneAsk what, int v, bool problem_major, bool ro
         {opt.barrier_cost, "\"lane_barrier_cost\" is", "set \"lane_barrier_cost\" to 0"},
         {opt.line_search != 0, "\"lane_line_search\" is", "set \"lane_line_search\" to 0"},
         {opt.models && model.box.on(), "a state box is", "clear it (i2lqr_set_state_box with NULL bounds)"},
-        {opt.models && model.obs > 1, "\"obstacles\" is", "set \"obstacles\" to 1"}};
+        {opt.models && model.obs > 1, "\"obstacles\" is", "set \"obstacles\" to 1"},
+        {opt.rows_models, "\"lane_rows_models\" is", "set \"lane_rows_models\" to 0"}};
+    for (const auto& h : held)
+      if (h.on && !on)
+        return lane_refuse(I2LQR_ERR_INVALID, "%s cannot be switched off while %s on: %s first",
+                           name, h.is, h.undo);
+    return LaneRefusal();
+  }
+  if (what == LANE_ASK_ROWS_MODELS) {
+    if (on && problem_major)
+      return lane_refuse(I2LQR_ERR_UNSUPPORTED, "%s is built for the batch-minor / batch-tiled "
+                         "layouts of quad12 (a problem-major handle runs the models on the "
+                         "one-problem-per-wavefront kernels without it)", name);
+    if (on && !rows)
+      return lane_refuse(I2LQR_ERR_UNSUPPORTED, "%s is built for quad12's row-block kernel "
+                         "(k_lane_iterate_rows): a bicycle handle runs the models with \"lane_models\" "
+                         "1 and needs nothing more", name);
+    if (on && !opt.models)
+      return lane_refuse(I2LQR_ERR_UNSUPPORTED, "%s runs on top of \"lane_models\": set "
+                         "\"lane_models\" to 1 first", name);
+    const struct { bool on; const char* is; const char* undo; } held[] = {
+        {opt.rows_models && model.box.on(), "a state box is", "clear it (i2lqr_set_state_box with NULL bounds)"},
+        {opt.rows_models && model.obs > 1, "\"obstacles\" is", "set \"obstacles\" to 1"}};
     for (const auto& h : held)
       if (h.on && !on)
         return lane_refuse(I2LQR_ERR_INVALID, "%s cannot be switched off while %s on: %s first",
@@ -166,7 +214,7 @@ inline LaneRefusal lane_refusal(LaneAsk what, int v, bool problem_major, bool ro
     return !lane_option ? refuse_layout(name)
                         : lane_refuse(I2LQR_ERR_UNSUPPORTED, "%s runs on the kernel of "
                                       "\"lane_models\": set \"lane_models\" to 1 first", name);
-  if (rows)
+  if (rows && (lane_option || !opt.rows_models))  // ("lane_rows_models": records and the box, nothing else)
     return lane_refuse(I2LQR_ERR_UNSUPPORTED, "%s with \"lane_models\" is built for the bicycles' "
                        "one-problem-per-lane kernel, not for quad12's row-block kernel "
                        "(k_lane_iterate_rows): use the problem-major layout", name);

@@ -218,6 +218,38 @@ inline LaneModelPlan lane_model_plan(const DeviceGeometry& g, const LaneShape& s
   return p;
 }
 
+// A model launch of a row-block plant ("lane_rows_models" 1; k_lane_iterate_rows_model,
+// i2lqr_lane_rows_model.hpp): ONE launch whatever the batch and whatever "lane_model_chunks" says, the
+// grid and the stagger of the plain k_lane_iterate_rows launch of that batch.  The kernel lives on four
+// workgroups per CU, so its LDS is static and the model adds nothing to it: records
+// 1 ... K - 1 are read from the obs rows at the step that uses them and the box is a by-value kernel
+// argument.  What it takes is the row-block pass's own slice, in words per wavefront
+// (LaneWorker::kGainWords, which asserts this formula): the step's [Kc | k], the obstacle terms, l_u,
+// the sin / cos values, the state entries of the second Jacobian evaluation, u, and the five
+// obstacle parameters of the pass - and the 64 words of the warm-up sink (budgeted in both word
+// sizes; fp32 never takes the hot pass that warms rows up, and the compiler drops its sink).
+constexpr int lane_rows_gain_words(int n, int m, int ntrig, int njx) {
+  return (m * (n + 1) + 5 + m + ntrig + njx + m + 5) * 64;
+}
+struct LaneRowsModelPlan {
+  unsigned grid;
+  int stagger;
+  size_t lds_bytes;  // static LDS of a workgroup (one wavefront)
+  bool fits;         // four workgroups per CU still fit: lds_bytes <= LDS per CU / 4
+};
+// gain_words: lane_rows_gain_words() of the plant
+inline LaneRowsModelPlan lane_rows_model_plan(const DeviceGeometry& g, const LaneShape& s,
+                                              const LaneTune& t, const LaneModel& md, int64_t B,
+                                              int gain_words) {
+  LaneRowsModelPlan p;
+  p.grid = lane_grid(B);
+  p.stagger = lane_options(g, s, t, B, false).stagger;
+  (void)md;  // records and the box take no LDS, whatever K and whichever sides are bounded
+  p.lds_bytes = (size_t)gain_words * (size_t)s.word + 64 * sizeof(unsigned);
+  p.fits = p.lds_bytes <= g.lds_per_cu / 4;
+  return p;
+}
+
 // Workspace (byte offsets from the registered base) for B problems: candidate inputs + gains
 // scratch + the second state buffer of the helper-wavefront form (every call), and for the chunked
 // solve two compacted work sets, scratch iters / status and one counter per round.  ONE table:

@@ -188,7 +188,14 @@ class BatchedILQR:
         not bicycle6 in fp32 with stage weights (such a solve stays a single launch).  The workspace grows by the records' rows of the two work
         sets: ensure_workspace() asks again before every call.  iterate(), iterate_pick() and batches
         under the threshold are unaffected; 0 / -1 off, the default: a model solve() is a single
-        launch).
+        launch).  Lane layouts of quad12: "lane_rows_models" (with "lane_models" 1 only; 1: the
+        solver accepts "obstacles" 2 ... 8 and set_state_box() as well and runs them on
+        k_lane_iterate_rows_model, the row-block kernel with the models in the backward pass's
+        derivatives; `obs` has the bicycles' model shapes; fp64 and fp32 with Q = R = 0 - with stage
+        weights a model launch is refused; every iterate() / solve() is a single launch and
+        "lane_model_chunks" has no effect; "lane_barrier_cost" and "lane_line_search" stay refused on
+        quad12; 0 / -1 off, refused while records or a box are on, and "lane_models" cannot be switched
+        off while it is on; with no model set the solver runs k_lane_iterate_rows, bit for bit).
         All but "wave_tail", "group_lanes", "line_search", "obstacles", "barrier_cost",
         "lane_barrier_cost" and "lane_line_search" leave the results bit-identical."""
         self._check(self.lib.i2lqr_set_option(self._handle, name.encode(), int(value)))
@@ -203,7 +210,8 @@ class BatchedILQR:
         bound is soft).  While a bound is finite every call runs on k_iterate_box, which composes
         with "obstacles" and "line_search"; set_state_box() with no finite bound switches it off
         (today's kernels, bit for bit).  A batch-minor / batch-tiled solver of the bicycles takes the
-        box after set_option("lane_models", 1) and runs it on k_lane_iterate_model.  `state_box`
+        box after set_option("lane_models", 1) and runs it on k_lane_iterate_model; one of quad12
+        after set_option("lane_rows_models", 1) as well, on k_lane_iterate_rows_model.  `state_box`
         holds (lo, hi, q1, q2) while it is on."""
         import numpy as np
         if lo is None and hi is None:

@@ -406,7 +406,8 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     I2LQR_ERR_UNSUPPORTED while a model is on.  Still I2LQR_ERR_UNSUPPORTED with
  *                     "lane_models" 1: "line_search" > 1 and "barrier_cost" 1 (such a handle has
  *                     "lane_line_search" and "lane_barrier_cost", below) and "wave_chain" 1 on such
- *                     a handle, and a model on quad12 (its row-block kernel has none).  With no
+ *                     a handle, and a model on quad12 (its row-block kernel has none; see
+ *                     "lane_rows_models" below for the kernel that has).  With no
  *                     model set the handle runs what it ran before.  -1 or 0: off (the default);
  *                     I2LQR_ERR_INVALID while "obstacles" > 1, a box, "lane_barrier_cost" or
  *                     "lane_line_search" is on (the
@@ -550,6 +551,30 @@ int i2lqr_set_compaction(i2lqr_handle* h, int64_t min_batch);
  *                     under the threshold and handles without a model are unaffected.  -1, 0 (the
  *                     default and the automatic choice): off - a model solve is ONE launch, as
  *                     written under "lane_models".
+ *   "lane_rows_models"  batch-minor / batch-tiled handles of quad12 whose "lane_models" is 1.  1: the
+ *                     handle accepts "obstacles" 2 ... I2LQR_MAX_OBSTACLES and i2lqr_set_state_box
+ *                     with finite bounds as well, with "lane_models"'s semantics word for word
+ *                     (record-order summation starting from the first enabled record's value,
+ *                     moving_option < 0 disables a record, a NULL obs all of them; the box's d1 / d2
+ *                     with unbounded sides masked and not computed; barriers in the derivatives only)
+ *                     and its obs layouts, obs[6][K][B] / obs[B/64][6][K][64].  While a model is on,
+ *                     i2lqr_iterate, i2lqr_solve and the unfused i2lqr_iterate_pick run
+ *                     k_lane_iterate_rows_model: k_lane_iterate_rows's loop, four workgroups per CU,
+ *                     the records beyond the first read from the obs rows at the step that uses them
+ *                     (no LDS beyond k_lane_iterate_rows's own; a device whose compute unit's LDS / 4
+ *                     does not hold it answers I2LQR_ERR_UNSUPPORTED), the box a kernel argument.
+ *                     fp64 and fp32 with Q = R = 0: with stage weights a launch with a model on is
+ *                     I2LQR_ERR_UNSUPPORTED (that instantiation is not built).  i2lqr_solve is ONE
+ *                     launch with early exit whatever the batch: "lane_model_chunks",
+ *                     i2lqr_set_compaction, "helper_wavefront", "checkpoint_states" and
+ *                     "state_buffers" have no effect; "stagger" applies.  "lane_barrier_cost" and
+ *                     "lane_line_search" stay I2LQR_ERR_UNSUPPORTED on quad12.  With no model set the
+ *                     handle runs and reports k_lane_iterate_rows, bit for bit.  -1 or 0: off (the
+ *                     default); I2LQR_ERR_INVALID while "obstacles" > 1 or a box is on, and
+ *                     "lane_models" 0 is I2LQR_ERR_INVALID while this option is on (the messages name
+ *                     what to clear first).  Any other value is I2LQR_ERR_INVALID.  1 is
+ *                     I2LQR_ERR_UNSUPPORTED on a problem-major handle, on a bicycle handle (there
+ *                     "lane_models" needs nothing more) and while "lane_models" is not 1.
  *   "stagger"         lane layouts (k_lane_iterate_rows, k_lane_iterate): every second half-thousand
  *                     of workgroups starts value x ~8000 cycles late, so that half of the
  *                     wavefronts stream their gains (forward pass) while the other half computes
@@ -587,7 +612,8 @@ int i2lqr_set_option(i2lqr_handle* h, const char* name, int64_t value);
  * i2lqr_iterate_pick takes its unfused form.
  * I2LQR_ERR_INVALID: a NaN bound, lo[i] >= hi[i], q1 <= 0 or q2 <= 0, exactly one pointer NULL.
  * I2LQR_ERR_UNSUPPORTED: a finite bound on a batch-minor / batch-tiled handle, unless its
- * "lane_models" is 1 (the bicycles: the same box on k_lane_iterate_model, see that option). */
+ * "lane_models" is 1 (the bicycles: the same box on k_lane_iterate_model, see that option) and, on
+ * quad12, its "lane_rows_models" as well (k_lane_iterate_rows_model). */
 int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, double q1, double q2);
 
 /* Name of the kernel i2lqr_iterate (fixed iteration count) launches for a batch of B problems
@@ -599,7 +625,8 @@ int i2lqr_set_state_box(i2lqr_handle* h, const double* lo, const double* hi, dou
  * (k_lane_iterate_merit with "lane_barrier_cost" 1: it ranks above the box),
  * "k_lane_iterate (line search)" (k_lane_iterate_ls with "lane_line_search" 2 / 4 / 8 and no other model: with one, the
  * kernel is k_lane_iterate_ls and the name is that model's, as on the problem-major side),
- * "k_lane_iterate_rows"; "unsupported" if a forced option cannot be honoured and the launch would
+ * "k_lane_iterate_rows", "k_lane_iterate_rows (several obstacles)", "k_lane_iterate_rows (state box)"
+ * (k_lane_iterate_rows_model with "lane_rows_models" 1: the box takes precedence); "unsupported" if a forced option cannot be honoured and the launch would
  * return I2LQR_ERR_UNSUPPORTED: what to look for in a rocprofv3 kernel trace.  The name comes from
  * the launcher's own decision code run on scratch arguments, not from a copy of its conditions.
  * Host only; "" for a NULL handle. */
